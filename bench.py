@@ -27,6 +27,14 @@ its wall time: the run fails if kernel ms per step exceeds ms_per_step by > 5 %.
   python bench.py [--gpus N --steps K --warmup W]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU, RCCL)
 
+A plain run sets up, warms up, times the K steps and prints the result line (throughput,
+ms_per_step and the roofline figures of the timed window's own launches).  --full adds what
+takes work of its own after the window: the Gelman-Rubin diagnostic over all chains of all
+GPUs (gelman_rubin_psrf, config.collective) and the CPU oracle baseline (cpu_baseline; omitted
+with --no-cpu-baseline).  --dump-outputs DIR writes what the timed run left for its caller
+(dump_outputs below) as DIR/<name>.npy; the inputs and seeds are fixed, so two builds run with
+the same arguments can be compared output for output.
+
 Other BASELINE configs (reported in DESIGN.md, not the metric line):
   --workload line_amm   configs[1]: line regression, AMM, 4096 chains per GPU
   --workload logistic   configs[3]: logistic N=10000 p=50, NUTS, 4096 chains per GPU
@@ -73,7 +81,13 @@ def parse():
     p.add_argument("--workload", default="rats",
                    choices=["rats", "line_amm", "logistic", "seeds_ir", "rats_ir", "rats_gibbs_ir"])
     p.add_argument("--thin", type=int, default=2)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed window also run the Gelman-Rubin diagnostic (and its collective) "
+                        "and the CPU oracle baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the timed run's outputs (chain state after the last step, the window's kept "
+                        "draws) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     p.add_argument("--cpu-seconds", type=float, default=20.0)
     p.add_argument("--nuts-burnin", type=int, default=None,
                    help="logistic: Model.burnin of the timed run (default steps // 2: 1000 of 2000)")
@@ -299,6 +313,28 @@ def seed_fullrank_moments(mb, model, eng):
     eng.set_tune(t)
 
 
+DUMP_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(eng, path, rank):
+    """--dump-outputs: what the timed eng.run(steps, keep_device=True) left for its caller, float64:
+    values.npy (chains x variates: every chain's state after the last timed step, Engine.values) and
+    draws.npy (kept iterations x monitored variates x chains: the window's Chains rows,
+    Engine.draws; the last row is the last kept step's).  chains.npy holds the chain index of each
+    column of draws / row of values: all of them, or, when that would exceed DUMP_BYTES, a fixed
+    seeded sample of chains (whole chains, every kept row).  Ranks above 0 write <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    v, d = eng.values(), eng.draws()
+    K = v.shape[0]
+    per_chain = 8 * (v.shape[1] + d.shape[0] * d.shape[1] + 1)
+    n = max(1, min(K, DUMP_BYTES // per_chain))
+    idx = np.arange(K) if n == K else np.sort(np.random.default_rng(20261015).choice(K, n, replace=False))
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    for name, arr in (("values", v[idx]), ("draws", d[:, :, idx]), ("chains", idx)):
+        np.save(os.path.join(path, name + sfx + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def lib_sha256():
     import hashlib
     import _mamba_path
@@ -441,6 +477,8 @@ def main():
     if nuts:
         after = eng.nuts_stats()
         nuts_timed = {k: after[k] - nuts_before[k] for k in after}
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank)
 
     # Gelman-Rubin over all chains of all GPUs: device partials + the library's own RCCL
     # communicator (mmb_comm_init / mmb_range_allreduce / mmb_gr_allreduce, the C-ABI collective
@@ -448,7 +486,7 @@ def main():
     # MMB_DIST_BACKEND=gloo (several ranks sharing one GPU, which RCCL refuses) reduces the same
     # device partials through torch.distributed on the host instead.
     psrf, coll_note = None, None
-    if backend == "nccl":
+    if args.full and backend == "nccl":
         # RCCL prints a version banner on stdout at communicator init: keep stdout for the one
         # JSON line (the banner goes to stderr)
         sys.stdout.flush()
@@ -471,7 +509,7 @@ def main():
             sys.stdout.flush()
             os.dup2(saved, 1)
             os.close(saved)
-    if backend == "nccl" and world > 1:
+    if args.full and backend == "nccl" and world > 1:
         # the fallback decision is collective too: one rank's local failure after the library's
         # agreement step sends every rank to the torch.distributed reduction (no rank left waiting)
         flag = torch.tensor([1.0 if psrf is None else 0.0], dtype=torch.float64, device=coll_dev)
@@ -480,7 +518,7 @@ def main():
             psrf = None
             coll_note = "library RCCL communicator failed on another rank; partials reduced through " \
                         "torch.distributed instead"
-    if psrf is None:
+    if args.full and psrf is None:
         def ar_sum(x):
             t = torch.tensor(x, dtype=torch.float64, device=coll_dev)
             dist.all_reduce(t)
@@ -590,11 +628,12 @@ def main():
                  else
                  "synthetic X ~ N(0,1), y ~ Bernoulli(invlogit(X beta_true)) (SURVEY §8d seeds); inits N(0, 0.1^2)"),
         "config": {"workload": desc, "chains_per_gpu": K, "global_chains": K * world, "thin": thin,
-                   "parallelism": f"chain-shard x{world}",
-                   "collective": ("rccl (mmb_gr_allreduce)" if backend == "nccl" and coll_note is None else
-                                  f"{backend} (torch.distributed)")},
+                   "parallelism": f"chain-shard x{world}"},
         "roofline": roof,
     }
+    if args.full:
+        out["config"]["collective"] = ("rccl (mmb_gr_allreduce)" if backend == "nccl" and coll_note is None else
+                                       f"{backend} (torch.distributed)")
     if args.workload != "rats":
         out["metric"] = f"chain-updates/sec on {args.workload} (not the headline metric)"
     if nuts:
@@ -623,7 +662,7 @@ def main():
         out["gelman_rubin_psrf"] = [float(x) for x in psrf[:, 0]]
     if coll_note is not None:
         out["config"]["collective_note"] = coll_note
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.workload == "rats":
             ref = rats_model(mb, scheme_for(mb, "reference"))
             out["cpu_baseline"] = cpu_baseline(model, init_all, args.cpu_seconds,

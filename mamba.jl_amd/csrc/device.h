@@ -12,7 +12,7 @@
 #include <stdint.h>
 #endif
 
-#include "../../include/mamba_hip.h"
+#include "mamba_hip.h"
 #include "mmb_math.h"
 #include "ir_math.h"
 

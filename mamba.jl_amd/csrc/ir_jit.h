@@ -3,7 +3,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/mamba_hip.h"
+#include "mamba_hip.h"
 
 // HIP source of the sweep kernel specialised for one lowered model: its node log densities and
 // block term lists as straight-line code, `kinds` = bitmask of the scheme's sampler kinds,

@@ -9,7 +9,7 @@
  */
 #ifndef MMB_IR_MATH_H
 #define MMB_IR_MATH_H
-#include "../../include/mamba_hip.h"
+#include "mamba_hip.h"
 #include "mmb_math.h"
 
 /* lgamma(x) for x > 0: shift to z >= 10 by the product x(x+1)...(x+k-1), then Stirling's

@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol(mamba):
     assert lib.mmb_abi_version() == mamba.abi.MMB_ABI_VERSION == 10
 
 
-def test_struct_layout_matches_header(mamba):
+def test_struct_layout_matches_header(mamba, tmp_path):
     src = """
 #include <stddef.h>
 #include <stdio.h>
@@ -39,8 +39,7 @@ int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mmb_block_spe
  offsetof(mmb_run_args, keep_device), offsetof(mmb_block_spec, epsilon), offsetof(mmb_block_spec, nsteps));
  return 0;}
 """
-    d = "/tmp/mmb_layout"
-    os.makedirs(d, exist_ok=True)
+    d = str(tmp_path)
     open(f"{d}/t.c", "w").write(src)
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", f"{d}/t", f"{d}/t.c"])
     got = list(map(int, subprocess.check_output([f"{d}/t"]).split()))

@@ -211,7 +211,7 @@ def test_bench_torchrun_two_ranks():
     env = dict(os.environ, MMB_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-           "--steps", str(steps), "--warmup", str(warmup), "--chains", str(K), "--no-cpu-baseline"]
+           "--steps", str(steps), "--warmup", str(warmup), "--chains", str(K), "--full", "--no-cpu-baseline"]
     # a fresh child process (this one may have touched the GPU: the launcher is started, never exec'd)
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]

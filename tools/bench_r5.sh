@@ -3,7 +3,7 @@
 set -e
 OUT=${1:-gpurun_out/r5bench}
 mkdir -p $OUT
-run() { n=$1; shift; echo "$n"; timeout -k 10 400 python bench.py "$@" > $OUT/$n.json 2> $OUT/$n.err; }
+run() { n=$1; shift; echo "$n"; timeout -k 10 400 python bench.py --full "$@" > $OUT/$n.json 2> $OUT/$n.err; }
 run rats_default
 run rats_driver --gpus 1 --steps 20 --warmup 5
 run rats_400 --steps 400 --warmup 20 --no-cpu-baseline

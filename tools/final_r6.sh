@@ -24,7 +24,7 @@ prof|prof_b)
     "tools/profiles_r6.sh $OUT/seeds_ir '--workload seeds_ir' mmb_ir_jit_kernel seeds 10" \
     "tools/profiles_r6.sh $OUT/rgir '--workload rats_gibbs_ir' mmb_ir_jit_kernel gibbs_amm 4" ;;
 bench)
-  run() { n=$1; shift; echo "$n"; timeout -k 10 400 python bench.py "$@" > $OUT/$n.json 2> $OUT/$n.err || return $?; }
+  run() { n=$1; shift; echo "$n"; timeout -k 10 400 python bench.py --full "$@" > $OUT/$n.json 2> $OUT/$n.err || return $?; }
   tools/gsafe.sh \
     "$(declare -f run); run rats_driver --gpus 1 --steps 20 --warmup 5" \
     "$(declare -f run); run rats_default" \

@@ -6,7 +6,7 @@ set -e
 OUT=${1:-gpurun_out/ir_bench}
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py --workload seeds_ir > $OUT/seeds_ir.json 2> $OUT/seeds_ir.err
-timeout -k 10 300 python bench.py --workload rats_ir > $OUT/rats_ir.json 2> $OUT/rats_ir.err
+timeout -k 10 300 python bench.py --full --workload seeds_ir > $OUT/seeds_ir.json 2> $OUT/seeds_ir.err
+timeout -k 10 300 python bench.py --full --workload rats_ir > $OUT/rats_ir.json 2> $OUT/rats_ir.err
 timeout -k 10 300 python bench.py --workload rats --scheme reference --no-cpu-baseline > $OUT/rats_ref.json 2> $OUT/rats_ref.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --workload seeds_ir --no-cpu-baseline > $OUT/trace.log 2>&1

@@ -16,7 +16,7 @@ LAST=${5:-10}
 mkdir -p $OUT
 export TMPDIR=/tmp
 ARGS="--no-cpu-baseline $BARGS"
-timeout -k 10 400 python bench.py $BARGS > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full $BARGS > $OUT/bench.json 2> $OUT/bench.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $ARGS > $OUT/trace.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- python3 bench.py $ARGS > $OUT/pmc_fetch.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o run -- python3 bench.py $ARGS > $OUT/pmc_write.log 2>&1

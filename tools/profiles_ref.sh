@@ -16,5 +16,5 @@ echo "pmc f64"
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $OUT/pmc_sq1 -o run -- python3 bench.py $ARGS > $OUT/pmc_sq1.log 2>&1
 python3 tools/profiles_pmc_summary.py $OUT $PREFIX --scheme reference
 echo "bench with the valu roofline"
-timeout -k 10 300 python bench.py --scheme reference > $OUT/bench_final.json 2> $OUT/bench_final.err
+timeout -k 10 300 python bench.py --full --scheme reference > $OUT/bench_final.json 2> $OUT/bench_final.err
 cp $OUT/bench_final.json ${PREFIX}_bench.json
