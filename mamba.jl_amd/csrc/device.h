@@ -226,22 +226,6 @@ __device__ __forceinline__ void fmac_rowbc(double& acc, double x, double b) {
     asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
                  : "+v"(acc) : "v"(x), "v"(b), "n"(N));
 }
-__device__ __forceinline__ void fmac_rowbc_nf(double& acc, double x, double b, int n, bool first);
-// acc = fma(-(x of lane n of the row), b, acc): the DPP word's src0 negate bit (exact), for a source
-// last written by an LDS read (no wait states, see fmac_rowbc_ld)
-template <int N>
-__device__ __forceinline__ void fmac_rowbc_neg(double& acc, double x, double b) {
-  asm volatile("v_fmac_f64_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-               : "+v"(acc) : "v"(x), "v"(b), "n"(N));
-}
-__device__ __forceinline__ void fmac_rowbc_ldneg(double& acc, double x, double b, int n) {
-  switch (n) {  // n is a constant after unrolling: one case survives
-#define MMB_RBC(i) case i: fmac_rowbc_neg<i>(acc, x, b); break;
-    MMB_RBC(0) MMB_RBC(1) MMB_RBC(2) MMB_RBC(3) MMB_RBC(4) MMB_RBC(5) MMB_RBC(6) MMB_RBC(7)
-    MMB_RBC(8) MMB_RBC(9) MMB_RBC(10) MMB_RBC(11) MMB_RBC(12) MMB_RBC(13) MMB_RBC(14) MMB_RBC(15)
-#undef MMB_RBC
-  }
-}
 // n = k % 16 of a dot product over k ascending: the uses at k = 0 and k = 16 are first uses
 __device__ __forceinline__ void fmac_rowbc_n(double& acc, double x, double b, int n) {
   switch (n) {  // n is a constant after unrolling: one case survives
@@ -256,30 +240,11 @@ __device__ __forceinline__ void fmac_rowbc_n(double& acc, double x, double b, in
 // read-after-VALU-write hazard does not apply and no use needs wait states (tests/test_isa.py
 // checks the built code for VALU writes of every DPP source)
 __device__ __forceinline__ void fmac_rowbc_ld(double& acc, double x, double b, int n) {
-#ifdef MMB_EXP_DPPNOP
-  fmac_rowbc_n(acc, x, b, n);
-#else
-  fmac_rowbc_nf(acc, x, b, n, false);
-#endif
-}
-
-// as fmac_rowbc_n with the first use of the source at an explicit step (a dot product whose
-// first products are formed otherwise)
-__device__ __forceinline__ void fmac_rowbc_nf(double& acc, double x, double b, int n, bool first) {
-  if (first) {
-    switch (n) {
-#define MMB_RBC(i) case i: fmac_rowbc<i, true>(acc, x, b); break;
-      MMB_RBC(0) MMB_RBC(1) MMB_RBC(2) MMB_RBC(3) MMB_RBC(4) MMB_RBC(5) MMB_RBC(6) MMB_RBC(7)
-      MMB_RBC(8) MMB_RBC(9) MMB_RBC(10) MMB_RBC(11) MMB_RBC(12) MMB_RBC(13) MMB_RBC(14) MMB_RBC(15)
-#undef MMB_RBC
-    }
-  } else {
-    switch (n) {
+  switch (n) {
 #define MMB_RBC(i) case i: fmac_rowbc<i, false>(acc, x, b); break;
-      MMB_RBC(0) MMB_RBC(1) MMB_RBC(2) MMB_RBC(3) MMB_RBC(4) MMB_RBC(5) MMB_RBC(6) MMB_RBC(7)
-      MMB_RBC(8) MMB_RBC(9) MMB_RBC(10) MMB_RBC(11) MMB_RBC(12) MMB_RBC(13) MMB_RBC(14) MMB_RBC(15)
+    MMB_RBC(0) MMB_RBC(1) MMB_RBC(2) MMB_RBC(3) MMB_RBC(4) MMB_RBC(5) MMB_RBC(6) MMB_RBC(7)
+    MMB_RBC(8) MMB_RBC(9) MMB_RBC(10) MMB_RBC(11) MMB_RBC(12) MMB_RBC(13) MMB_RBC(14) MMB_RBC(15)
 #undef MMB_RBC
-    }
   }
 }
 

@@ -11,7 +11,7 @@
 //   * the Philox blocks: lane e < 3 draws normal pair e of the NORMAL substream (z1[e],
 //     z2[e]), lane 3 block 0 of the UNIFORM substream (the accept uniform); they do not depend
 //     on the chain state, so a second wavefront of the workgroup draws them one iteration ahead
-//     into LDS (MMB_LINE_RNGWAVE, round 6: 6.13e8 -> 6.87e8; before, the update wavefront drew
+//     into LDS (the draws wavefront, round 6: 6.13e8 -> 6.87e8; before, the update wavefront drew
 //     the next iteration's inside its own loop), and the quad shares them by DPP quad_perm
 //     broadcasts;
 //   * logpdf: lane 0 evaluates logf(x), lane 1 logf(v), each on its own relisted state, which
@@ -316,18 +316,14 @@ __device__ __forceinline__ void line_draw(const SweepArgs& A, uint32_t chain, in
 }
 }  // namespace
 
-#ifndef MMB_LINE_RNGWAVE
-#define MMB_LINE_RNGWAVE 1
-#endif
-// MMB_LINE_RNGWAVE: each workgroup is two wavefronts over the same 16 chains -- wavefront 0 runs
+// Each workgroup is two wavefronts over the same 16 chains -- wavefront 0 runs
 // the updates, wavefront 1 (on another SIMD of the CU) draws each iteration's Philox blocks one
 // iteration ahead into an LDS ring of two slots, exactly as line_draw did inside the update loop;
 // one workgroup barrier per iteration hands a slot over.  The draws leave the update wavefront's
 // instruction stream (a timing build without them ran 17 % faster); the values are the same.
-constexpr int LWG = MMB_LINE_RNGWAVE ? 128 : 64;  // threads per workgroup
+constexpr int LWG = 128;  // threads per workgroup: the update wavefront and the draws wavefront
 
 __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
-#if MMB_LINE_RNGWAVE
   __shared__ double ring[2][3][64];  // [slot][n0, n1, u][lane of the update wavefront]
   const int tl = (int)(threadIdx.x & 63);
   const int c = (int)((blockIdx.x * 64 + tl) / LQ);
@@ -348,10 +344,6 @@ __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
     return;
   }
   if (c >= Ak.K) return;  // whole quads exit together (the wavefront keeps its in-range quads)
-#else
-  const int c = (int)((blockIdx.x * blockDim.x + threadIdx.x) / LQ);
-  if (c >= Ak.K) return;  // whole quads exit together
-#endif
   const int lane = (int)(threadIdx.x & (LQ - 1));
   const Grp<1> g1;  // the replicated (one-lane) arithmetic of Mdl<LINE>
   // the descriptor and the arguments the update loop reads, copied once into registers: read
@@ -368,7 +360,6 @@ __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
   for (int i = 0; i < 5; ++i) asm volatile("" : "+v"(A.lx[i]), "+v"(A.ly[i]));
   const int d = B.d;
   const int T = mmb_tri(d);
-  const uint32_t chain = A.chain_offset + (uint32_t)c;
 #ifdef MMB_PHASE_PROF
   if ((threadIdx.x & 63) == 0)
     for (int i = 0; i < 16; ++i) mmb_prof_lds()[i] = 0;
@@ -399,11 +390,7 @@ __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
   double v[3];
   ML::unlist(B, s, 0, v);
   double n0, n1, uown;
-#if MMB_LINE_RNGWAVE
   __syncthreads();  // slot 0 holds the first iteration's draws
-#else
-  line_draw(A, chain, A.iter0 + 1, lane, n0, n1, uown);
-#endif
   uint32_t st_fac = 0, st_full = 0, st_rank = 0, st_steps = 0, st_redo = 0;  // mmb_amm_stats
 
   for (int step = 0; step < A.n_iters; ++step) {
@@ -424,11 +411,9 @@ __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
     const double q = 1.0 - p;
     const double cc = sc2 / p;
     // this iteration's draws (drawn one iteration ahead) to the whole quad
-#if MMB_LINE_RNGWAVE
     n0 = ring[step & 1][0][threadIdx.x];
     n1 = ring[step & 1][1][threadIdx.x];
     uown = ring[step & 1][2][threadIdx.x];
-#endif
     double z1[3], z2[3];
     z1[0] = qbc<0>(n0); z2[0] = qbc<0>(n1);
     z1[1] = qbc<1>(n0); z2[1] = qbc<1>(n1);
@@ -439,10 +424,6 @@ __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
       z1[r] = r < d ? z1[r] : 0.0;
       z2[r] = r < d ? z2[r] : 0.0;
     }
-#if !MMB_LINE_RNGWAVE
-    // the next iteration's draws: an independent instruction stream for the scheduler
-    line_draw(A, chain, it + 1, lane, n0, n1, uown);
-#endif
     MMB_PROF_MARK(1, lane)
     // proposal: x = SigmaL z1 [; beta x + (1 - beta) SigmaLm z2]; x += v  (amm.jl:72-76)
     double x[3];
@@ -564,9 +545,7 @@ __global__ __launch_bounds__(LWG) void line_amm_kernel(const SweepArgs Ak) {
       ML::write_draws(A, s, g1, row, c);
     }
     MMB_PROF_MARK(6, lane)
-#if MMB_LINE_RNGWAVE
     __syncthreads();  // this slot read, the next one written
-#endif
   }
 #ifdef MMB_PHASE_PROF
   if ((threadIdx.x & 63) == 0) {

@@ -250,12 +250,10 @@ struct Mdl<MMB_MODEL_RATS> {
   __device__ __forceinline__ static void logf_p2(const SweepArgs& A, const DBlock& B, const Prep& c, const St& s,
                                                  const Lc& l, const Grp<G>& g, const double* x, const double* v,
                                                  double& lx, double& lv) {
-#ifndef MMB_EXP_LOGF1
     if (is_vec(B.nodes[0])) {
       logf_vec2(A, c, s, l, g, x, v, lx, lv);
       return;
     }
-#endif
     lx = logf_p(A, B, c, s, l, g, x);
     lv = logf_p(A, B, c, s, l, g, v);
   }

@@ -216,8 +216,11 @@ struct Smp {
   // factor row is broadcast through `prow` (contiguous LDS) each step.  On full rank the
   // factor is written back in place: L[i][step k] -> slot(i, piv[k]), L[i][pos_i] ->
   // slot(i,i).  pk[] receives the pivot order.  Returns the rank (group-uniform).
+  // One lane per chain holds every row (line: G = 1, R = 3); 32-lane groups with one row per
+  // lane (rats, the node IR) take pchol32 below, amm() decides.
   __device__ __forceinline__ static int pchol(int d, double* mat, double* prow, int* pks,
                                               const Grp<G>& g) {
+    static_assert(G == 1, "pchol()'s pivot search walks the rows of one lane; lane groups use pchol32");
     double diag0[R], work[R], Lrow[R][DMAX];
     bool done[R];
 #pragma unroll
@@ -235,94 +238,42 @@ struct Smp {
     for (int j = 0; j < DMAX; ++j) {
       if (live && j < d) {
         // ---- pivot: first maximum of the remaining diagonal in position order ----
-        double dl[R], cand[R];
+        double dl[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-          dl[r] = diag0[r] - work[r];
-          cand[r] = done[r] ? -__builtin_inf() : dl[r];
+        for (int r = 0; r < R; ++r) dl[r] = diag0[r] - work[r];
+        // dpstf2's position swaps replayed from the pivot history
+        int perm[DMAX];
+#pragma unroll
+        for (int t = 0; t < DMAX; ++t) perm[t] = t;
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) {
+          if (k < j) {
+            int q = pks[k];
+            int qpos = k;
+#pragma unroll
+            for (int t = 0; t < DMAX; ++t) qpos = (t >= k && perm[t] == q) ? t : qpos;
+            int tmp = perm[k];
+#pragma unroll
+            for (int t = 0; t < DMAX; ++t) perm[t] = (t == qpos) ? tmp : perm[t];
+            perm[k] = q;
+          }
         }
-        int p;
-        double val;
-#ifdef MMB_EXP_NOPIVOT
-        if (G == 32) {  // timing experiment only: no pivot search
-          p = j;
-          val = __shfl(dl[0], (int)(threadIdx.x & 32) + j, 64);
-        } else
-#endif
-        if (G == 32) {
-          // fast path: max-reduce, then the (usually unique) lane holding it
-          double mx = cand[0];
-          bool anynan = isnan(mx);
-          mx = anynan ? -__builtin_inf() : mx;
-          mx = fmax(mx, Grp<G>::template other_d<0>(mx));
-          mx = fmax(mx, Grp<G>::template other_d<1>(mx));
-          mx = fmax(mx, Grp<G>::template other_d<2>(mx));
-          mx = fmax(mx, Grp<G>::template other_d<3>(mx));
-          mx = fmax(mx, Grp<G>::template other_d<4>(mx));
-          const unsigned long long bw = __ballot(!done[0] && cand[0] == mx);
-          const unsigned long long bn = __ballot(!done[0] && anynan);
-          const unsigned sh = threadIdx.x & 32;
-          const unsigned win = (unsigned)(bw >> sh), nan_ = (unsigned)(bn >> sh);
-          if (__builtin_popcount(win) == 1 && nan_ == 0) {
-            p = __builtin_ctz(win);
-            val = mx;
-          } else {
-            // rare: exact tie or NaN -> replay dpstf2's position swaps (pks history)
-            int* perm = (int*)prow;  // group-private LDS scratch
-            if (g.lane == 0) {
-              for (int t = 0; t < d; ++t) perm[t] = t;
-              for (int k = 0; k < j; ++k) {
-                int q = pks[k], qpos = k;
-                for (int t = k; t < d; ++t) if (perm[t] == q) qpos = t;
-                int tmp = perm[k]; perm[k] = q; perm[qpos] = tmp;
-              }
-            }
-            grp_sync();
-            int mypos = 0x7fffffff;
-            for (int t = j; t < d; ++t) if (perm[t] == g.lane) mypos = t;
-            grp_sync();
-            double key = done[0] ? -__builtin_inf()
-                                 : (isnan(dl[0]) ? (mypos == j ? __builtin_inf() : -__builtin_inf()) : dl[0]);
-            int pi = (done[0] ? 0x7fff : mypos) << 16 | g.lane;
-            g.argmax(key, pi);
-            p = pi & 0xffff;
-            val = g.bcast(dl[0], p);
+        // fold in position order: first strict maximum (oracle.c orc_pchol)
+        int best = -1;
+        double bv = 0.0;
+#pragma unroll
+        for (int t = 0; t < DMAX; ++t) {
+          if (t >= j && t < d) {
+            int e = perm[t];
+            double de = dl[0];
+#pragma unroll
+            for (int r = 1; r < R; ++r) de = (e == r) ? dl[r] : de;
+            if (best < 0) { best = e; bv = de; }
+            else if (de > bv) { best = e; bv = de; }
           }
-        } else {
-          // sequential lanes (G == 1): replay positions per chain
-          int perm[DMAX];
-#pragma unroll
-          for (int t = 0; t < DMAX; ++t) perm[t] = t;
-#pragma unroll
-          for (int k = 0; k < DMAX; ++k) {
-            if (k < j) {
-              int q = pks[k];
-              int qpos = k;
-#pragma unroll
-              for (int t = 0; t < DMAX; ++t) qpos = (t >= k && perm[t] == q) ? t : qpos;
-              int tmp = perm[k];
-#pragma unroll
-              for (int t = 0; t < DMAX; ++t) perm[t] = (t == qpos) ? tmp : perm[t];
-              perm[k] = q;
-            }
-          }
-          // fold in position order: first strict maximum (oracle.c orc_pchol)
-          int best = -1;
-          double bv = 0.0;
-#pragma unroll
-          for (int t = 0; t < DMAX; ++t) {
-            if (t >= j && t < d) {
-              int e = perm[t];
-              double de = dl[0];
-#pragma unroll
-              for (int r = 1; r < R; ++r) de = (e == r) ? dl[r] : de;
-              if (best < 0) { best = e; bv = de; }
-              else if (de > bv) { best = e; bv = de; }
-            }
-          }
-          p = best;
-          val = bv;
         }
+        const int p = best;
+        const double val = bv;
         if (!(val > 0.0)) {
           rank = j;
           live = false;
@@ -347,7 +298,6 @@ struct Smp {
             int e = r * G + g.lane;
             if (!done[r]) {
               double t0 = 0.0, t1 = 0.0;
-#ifndef MMB_EXP_NODOT
 #pragma unroll
               for (int k = 0; k + 1 < j; k += 2) {
                 const double2 pp = *(const double2*)(prow + k);
@@ -355,7 +305,6 @@ struct Smp {
                 t1 = fma(Lrow[r][k + 1], pp.y, t1);
               }
               if (j & 1) t0 = fma(Lrow[r][j - 1], prow[j - 1], t0);
-#endif
               double lij = (mat[mmb_slot(e, p)] - (t0 + t1)) * rinv;
               Lrow[r][j] = lij;
               work[r] = work[r] + lij * lij;
@@ -429,73 +378,6 @@ struct Smp {
     return max((int)r[0], (int)r[1]);
   }
 
-  // The checked factorization as a compact loop (not unrolled; the row lives in a private
-  // array): the rare redo after an optimistic pass of pchol32 that met a tie, a NaN or a
-  // maximum outside the in-range square root's domain.  dpstf2's pivot (pivot_exact: first
-  // maximum in position order, NaN semantics) and its ajj <= 0 stop, IEEE sqrt() and 1.0 / x,
-  // and the same two-accumulator dot product (even / odd k) as the unrolled steps, so the
-  // factor is bit-identical to what the checked unrolled pass computes.  Leaves the rows in
-  // Lrow[], the positions in pe, done / work as the unrolled pass does.
-#ifdef MMB_REDO_INLINE
-  __device__ __forceinline__
-#else
-  __device__ __attribute__((noinline))
-#endif
-  static void redo_exact_impl(int d, double* mat, double* prow, int* pks,
-                                                                    double diag0, int lc, bool inb, double* Lx,
-                                                                    double* work_, bool* done_, int* pe_) {
-    const int lane = (int)(threadIdx.x & (G - 1));
-    double work = inb ? 0.0 : __builtin_inf();
-    bool done = !inb, live = true;
-    int pe = 0;
-    for (int k = 0; k < DMAX; ++k) Lx[k] = 0.0;
-#pragma nounroll
-    for (int j = 0; j < d; ++j) {
-      if (live) {
-        const double dl = diag0 - work;
-        double val;
-        const int p = pivot_exact(dl, done, pks, j, d, (int*)prow, &val);
-        if (!(val > 0.0)) {
-          live = false;
-        } else {
-          if (lane == p) {
-            pks[j] = p;
-            for (int k = 0; k < j; ++k) prow[k] = Lx[k];
-            const double ajj = sqrt(dl);
-            prow[DMAX] = 1.0 / ajj;
-            Lx[j] = ajj;
-            pe = j;
-            work = __builtin_inf();
-            done = true;
-          }
-          grp_sync();
-          if (j + 1 < d) {
-            double t0 = 0.0, t1 = 0.0;
-            for (int k = 0; k < j; ++k) {
-              if (k & 1) t1 = fma(prow[k], Lx[k], t1);
-              else t0 = fma(prow[k], Lx[k], t0);
-            }
-            const double lij = (mat[mmb_slot(lc, p)] - (t0 + t1)) * prow[DMAX];
-            work = work + lij * lij;
-            if (!done) Lx[j] = lij;
-          }
-          grp_sync();
-        }
-      }
-    }
-    *work_ = work;
-    *done_ = done;
-    *pe_ = pe;
-  }
-  __device__ __forceinline__ static void redo_exact(int d, double* mat, double* prow, int* pks, double diag0,
-                                                    int lc, bool inb, double (&Lrow)[DMAX], double& work,
-                                                    bool& done, int& pe) {
-    double Lx[DMAX];
-    redo_exact_impl(d, mat, prow, pks, diag0, lc, inb, Lx, &work, &done, &pe);
-#pragma unroll
-    for (int k = 0; k < DMAX; ++k) Lrow[k] = Lx[k];
-  }
-
   // pchol for 32-lane groups with one row per lane (rats), same results as pchol():
   // * the pivot lane computes sqrt / reciprocal of its remaining diagonal by the in-range
   //   sequences of device.h (bit-identical to sqrt() and 1.0 / x there) and publishes the
@@ -518,24 +400,14 @@ struct Smp {
                                                 int* pos_out, const DBlock* NB = nullptr,
                                                 const SweepArgs& A = SweepArgs{}, int c = 0, uint32_t chain = 0,
                                                 int64_t it = 0, int b = 0, int m = 0, int* redo = nullptr) {
-#ifndef MMB_PCHOL_NOFULLD
     // a block as wide as the model's DMAX (rats: both 30-d blocks) runs a copy with d a
     // compile-time constant: no per-step scalar test and branch of j against d (9.58e7 ->
     // 9.90e7 rats chain-updates/s, A/B on one box, parity unchanged)
     if (d == DMAX)
-      return pchol32_impl<true, true>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo);
-#endif
-    return pchol32_impl<true>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo);
+      return pchol32_impl<true>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo);
+    return pchol32_impl<false>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo);
   }
-#if !defined(MMB_PCHOL_V1) && defined(MMB_PCHOL_EXACT_NOINLINE)
-  // timing experiment: the checked pass (rare) out of line (measured 13 % slower: call ABI)
-  __device__ __noinline__ static int pchol32_exact(int d, double* mat, double* prow, int* pks, int* pos_out,
-                                                   const DBlock* NB, uint64_t seed, int64_t xepoch, int c,
-                                                   uint32_t chain, int64_t it, int b, int m) {
-    return pchol32_impl<false>(d, mat, prow, pks, pos_out, NB, seed, xepoch, c, chain, it, b, m, nullptr);
-  }
-#endif
-  template <bool OPT, bool FULLD = false>
+  template <bool FULLD>
   __device__ __forceinline__ static int pchol32_impl(int d_arg, double* mat, double* prow, int* pks, int* pos_out,
                                                      const DBlock* NB, uint64_t seed, int64_t xepoch, int c,
                                                      uint32_t chain, int64_t it, int b, int m,
@@ -571,17 +443,6 @@ struct Smp {
         if (m > 2 * d) {
           // rows are zero past the lane's own step, so the full sweep adds exact zeros
           double y = 0.0;
-#ifdef MMB_EXP_LDS_CARRY
-          prow[lane] = z2n;
-          grp_sync();
-#pragma unroll
-          for (int k = 0; k < DMAX; k += 2) {
-            const double2 zz = *(const double2*)(prow + k);
-            y = fma(Lrow[k], zz.x, y);
-            if (k + 1 < DMAX) y = fma(Lrow[k + 1], zz.y, y);
-          }
-          grp_sync();
-#else
           // z2'[k] lives in lane k: rows 0 / 1 of the group exchange theirs (permlane16 swap),
           // then each product takes z2'[k] from lane k % 16 of the row (DPP64 row_newbcast)
           const double zs = swap16_d(z2n);
@@ -589,7 +450,6 @@ struct Smp {
           const double zA = row0 ? z2n : zs, zB = row0 ? zs : z2n;
 #pragma unroll
           for (int k = 0; k < DMAX; ++k) fmac_rowbc_n(y, k < 16 ? zA : zB, Lrow[k], k & 15);
-#endif
           a = NB->beta * a + (1.0 - NB->beta) * y;
         }
         if (inb) NB->t_xnext[(size_t)c * DP + lane] = a;
@@ -610,14 +470,13 @@ struct Smp {
       *pos_out = pe;
       return rank;
     };
-#ifndef MMB_PCHOL_V1
     // Two passes over the same Sigma (mat is only read until the write-back):
     // * the optimistic pass takes, per chain, the lane whose candidate dl = diag0 - work has
     //   the largest int32 high word (the lowest such lane on a tie) as the pivot and stops
-    //   when every candidate is negative.  It never branches on the pivot search; it only
-    //   accumulates, on the scalar unit, whether a step was outside what that rule decides
-    //   exactly: a high-word tie, a NaN or >= 2^700 candidate, or a maximum below 2^-700
-    //   (then the in-range square root / reciprocal of device.h would not be the IEEE ones);
+    //   when every candidate is negative.  It never branches on the pivot search; whether a
+    //   step was outside what that rule decides exactly -- a high-word tie, a NaN or >= 2^700
+    //   candidate, or a maximum below 2^-700 (then the in-range square root / reciprocal of
+    //   device.h would not be the IEEE ones) -- is checked once, after its last step;
     // * only if so (rare), the whole factorization is redone by the checked pass: the same
     //   steps, with dpstf2's exact choice (pivot_exact: first maximum in position order, its
     //   rank test) and sqrt() / division wherever a step needs them.
@@ -632,76 +491,38 @@ struct Smp {
     asm volatile("" : "+v"(hmask));  // keep it a VGPR (not a scalar lane mask + select)
     constexpr int KEY_LO = 0x14300000;     // high word of 2^-700
     constexpr double BIG = 0x1p700;
-    // CHECKED: template constant (two inlined copies of the pass) or, with MMB_PCHOL_ONECOPY,
-    // a wave-uniform run-time flag that one copy of the pass branches on per step
+    // CHECKED is a template constant: two inlined copies of the pass (one copy branching per step
+    // on a run-time flag was tried and dropped).  The optimistic pass (!CHECKED)
+    // * keeps no per-step bookkeeping of whether its choices were dpstf2's: everything that could
+    //   make them differ is visible after the loop (see the check below the step loop; the round-3
+    //   per-step check cost scalar work in every step);
+    // * keeps no done flag: a lane is done iff its work is +inf (pivots set it; an undone lane
+    //   whose sum of squares overflowed counts as done too, which only a chain that cannot reach
+    //   full rank can meet -- its rank then disagrees with its steps and the check redoes it).
+    // Returns whether the pass has to be redone (the checked pass: never).
     auto pass = [&](auto checked_c) __attribute__((always_inline)) -> bool {
-#ifdef MMB_PCHOL_ONECOPY
-      const bool CHECKED = checked_c;
-#else
       constexpr bool CHECKED = decltype(checked_c)::value;
-#endif
-      // POSTHOC (default): the optimistic pass keeps no per-step bookkeeping of whether its
-      // choices were dpstf2's; everything that could make them differ is visible after the loop
-      // (see the check below the step loop).  MMB_PCHOL_STEPCHECK: the round-3 per-step check.
-#ifdef MMB_PCHOL_STEPCHECK
-      constexpr bool POSTHOC = false;
-#else
-      constexpr bool POSTHOC = !CHECKED;
-#endif
-      // DW: the optimistic pass keeps no done flag: a lane is done iff its work is +inf (pivots set
-      // it; an undone lane whose sum of squares overflowed counts as done too, which only a chain
-      // that cannot reach full rank can meet -- its rank then disagrees with its steps and the
-      // post-hoc check redoes it)
-#ifdef MMB_PCHOL_DONEFLAG
-      constexpr bool DW = false;
-#else
-      constexpr bool DW = POSTHOC;
-#endif
-      uint64_t needm = 0;  // wave-uniform: nonzero if a step of this pass was not decided exactly
-      bool needl = false;  // per-lane form of needm (a lane mask: the OR stays on the scalar unit)
-      double apiv = 1.0;   // POSTHOC: this lane's candidate when it was taken as the pivot
+      double apiv = 1.0;  // optimistic pass: this lane's candidate when it was taken as the pivot
       double inf_s = __builtin_inf();
       asm volatile("" : "+s"(inf_s));  // +inf in an SGPR pair: one v_mov_b64 per pivot
-#ifdef MMB_KEEPMASK
-      // DW: the lanes that took a pivot (or are out of range) as a lane mask on the scalar unit, so
-      // the row update's keep select needs no per-step compare of work against +inf
-      uint64_t donem = __ballot(!inb);
-#endif
 #pragma unroll
       for (int j = 0; j < DMAX; ++j) {
         if (live && j < d) {
           const double dl = diag0 - work;
-#ifdef MMB_EXP_HOIST
-          // every lane's square root and reciprocal, independent of the search: the two
-          // dependency chains interleave (the pivot lane then publishes at once)
-          double ajj_h = 0.0, rinv_h = 0.0;
-          if (!CHECKED) {
-            mmb_sqrt_rcp_inrange(dl, &ajj_h, &rinv_h);
-            asm volatile("" : "+v"(ajj_h), "+v"(rinv_h));
-          }
-#endif
           const int key = (int)(mmb_d2u(dl) >> 32);
           const int mx = gmax_i32(key);
           const uint64_t eq = __ballot(key == mx);
           uint32_t elo = (uint32_t)eq, ehi = (uint32_t)(eq >> 32);
           int p = 0;
-          // one compare for the stop and the bookkeeping's ballot (pos = the complement mask)
+          // one compare for the stop and the pivot mask (pos = the complement mask)
           const uint64_t negm = __ballot(mx < 0);
           bool pos = mmb_inverse_ballot(~negm);  // dpstf2's ajj <= 0 stop
           bool fast = true;
-#ifdef MMB_PCHOL_ONECOPY
-          {
-            const int plo = __builtin_ctz(elo | 0x80000000u), phi = __builtin_ctz(ehi | 0x80000000u);
-            p = plo ^ ((plo ^ phi) & hmask);
-          }
-          if (CHECKED) {
-#else
           if constexpr (!CHECKED) {
             // p = plo in the lower chain, phi in the upper one, as plo ^ ((plo ^ phi) & hmask)
             const int plo = __builtin_ctz(elo | 0x80000000u), phi = __builtin_ctz(ehi | 0x80000000u);
             p = plo ^ ((plo ^ phi) & hmask);
           } else {
-#endif
             const uint64_t act = __builtin_amdgcn_read_exec();
             const uint64_t bad = __ballot(!(dl < BIG));      // NaN, +inf or >= 2^700
             const uint64_t big = __ballot(key >= KEY_LO);    // candidates >= 2^-700
@@ -723,30 +544,21 @@ struct Smp {
               pos = val > 0.0;
             }
           }
-#ifdef MMB_PCHOL_STOPBR
-          constexpr bool NOBR = false;
-#else
           // optimistic pass: no branch on the stop either -- a chain whose candidates are all
           // negative runs this step on a garbage pivot (one of its done / out-of-range lanes,
           // whose -inf keys are the largest negative ones) and stops after it; a stopped
           // chain's factor is never used (rank < d) and its done set is unchanged
-          constexpr bool NOBR = !CHECKED;
-#endif
-          if (!NOBR && !pos) {
+          if (CHECKED && !pos) {
             live = false;  // rank = pivots taken, counted after the loop
           } else {
             // optimistic pass: the pivot is the lane holding the maximal high word (unique, or
             // the pass is redone; a stopping chain's garbage step may take several of its done /
-            // out-of-range -inf lanes, which changes nothing that is used)
-            // POSTHOC: no pivot on a stopping chain's step (its done lanes keep pe and row)
-            const bool piv = CHECKED ? lane == p
-                                     : POSTHOC ? mmb_inverse_ballot(eq & ~negm) : key == mx;
-#ifdef MMB_KEEPMASK
-            if constexpr (DW) donem |= eq & ~negm;
-#endif
+            // out-of-range -inf lanes, which changes nothing that is used), and a stopping
+            // chain's step takes no pivot (its done lanes keep pe and row)
+            const bool piv = CHECKED ? lane == p : mmb_inverse_ballot(eq & ~negm);
             if (piv) {
-              if constexpr (POSTHOC) apiv = dl;  // (pks: only the checked pass replays it)
-              else pks[j] = p;
+              if constexpr (CHECKED) pks[j] = p;  // (only the checked pass replays it)
+              else apiv = dl;
               if (j + 1 < d) {  // the last step has no rows left to update: no readers
 #pragma unroll
                 for (int k = 0; k + 1 < j; k += 2) *(double2*)(prow + k) = make_double2(Lrow[k], Lrow[k + 1]);
@@ -754,12 +566,6 @@ struct Smp {
               }
               double ajj, rinv;
               if (fast) {
-#ifdef MMB_EXP_HOIST
-                if (!CHECKED) {
-                  ajj = ajj_h;
-                  rinv = rinv_h;
-                } else
-#endif
                 mmb_sqrt_rcp_inrange(dl, &ajj, &rinv);  // IEEE results in the fast range (device.h)
               } else {
                 ajj = sqrt(dl);
@@ -769,7 +575,7 @@ struct Smp {
               Lrow[j] = ajj;
               pe = j;
               work = inf_s;
-              if constexpr (!DW) done = true;
+              if constexpr (CHECKED) done = true;
             }
             grp_sync();
             if (j + 1 < d) {  // (j = d - 1: every lane is done)
@@ -788,26 +594,6 @@ struct Smp {
               double pB = j > 16 ? prow[16 + (lane & 15)] : 0.0;
               asm volatile("" : "+v"(sig), "+v"(rinv), "+v"(pA));
               if (j > 16) asm volatile("" : "+v"(pB));
-#ifdef MMB_EXP_MUL01
-              // the first two products by plain multiplies of a broadcast read of the row's first
-              // pair (fma(a, b, 0) and a * b are the same value): no accumulator zeroing per step
-              if (j > 0) {
-                const double2 p01 = *(const double2*)prow;
-                t0 = p01.x * Lrow[0];
-                if (j > 1) t1 = p01.y * Lrow[1];
-#pragma unroll
-                for (int k = 2; k < j; ++k) {
-                  const double src = k < 16 ? pA : pB;
-                  if (k & 1) fmac_rowbc_nf(t1, src, Lrow[k], k & 15, k == 2 || k == 16);
-                  else fmac_rowbc_nf(t0, src, Lrow[k], k & 15, k == 2 || k == 16);
-                }
-#elif defined(MMB_SIGCHAIN)
-              // one accumulator seeded with Sigma(lane, p): t = fma(-prow[k], L[k], t), k ascending
-              (void)t0; (void)t1;
-              if (j > 0) {
-#pragma unroll
-                for (int k = 0; k < j; ++k) fmac_rowbc_ldneg(sig, k < 16 ? pA : pB, Lrow[k], k & 15);
-#else
               if (j > 0) {
 #pragma unroll
                 for (int k = 0; k < j; ++k) {
@@ -815,49 +601,21 @@ struct Smp {
                   if (k & 1) fmac_rowbc_ld(t1, src, Lrow[k], k & 15);
                   else fmac_rowbc_ld(t0, src, Lrow[k], k & 15);
                 }
-#endif
               }
-#ifdef MMB_SIGCHAIN
-              const double lij = sig * rinv;
-#else
               const double lij = (sig - (t0 + t1)) * rinv;
-#endif
-#ifdef MMB_KEEPMASK
-              const bool keep = DW ? mmb_inverse_ballot(donem) : done;  // done lanes keep their rows
-#else
-              const bool keep = DW ? work == inf_s : done;  // done lanes keep their rows
-#endif
+              const bool keep = CHECKED ? done : work == inf_s;  // done lanes keep their rows
               // done lanes carry work = +inf, which absorbs lij^2: no select for work
               work = work + lij * lij;
               if (!keep) Lrow[j] = lij;
             }
             grp_sync();
-            if (NOBR) live = live && pos;
-          }
-#ifndef MMB_PCHOL_ONECOPY
-          if constexpr (!CHECKED && !POSTHOC)
-#endif
-          {
-            // scalar bookkeeping off the step's dependency chain (after the row update, no
-            // branch): ties of a chain that takes a pivot, NaN / huge candidates, tiny maxima
-#ifdef MMB_EXP_SCHEDB
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-            const uint64_t bad = __ballot(!(dl < BIG));                     // NaN, +inf, >= 2^700
-            const uint64_t tiny = __ballot((uint32_t)mx < (uint32_t)KEY_LO);  // 0 <= max < 2^-700
-            const uint64_t neg = negm;
-            uint32_t nlo = (uint32_t)neg, nhi = (uint32_t)(neg >> 32);
-            asm("" : "+s"(elo), "+s"(ehi), "+s"(nlo), "+s"(nhi));
-            // (a stopping chain's -inf keys tie: ignored.  A live lane cannot share the done lanes'
-            // -inf key here: with every diagonal below 2^700 and every pivot above 2^-700, as this
-            // pass checks, |lij| <= sqrt(Sigma_ll) < 2^350 for the PSD moment matrix, so work
-            // stays finite; a -inf diagonal needs an overflowed Mv^2, whose Mvv is inf too: NaN.)
-            const uint32_t tie = ((elo & (elo - 1)) & (nlo ? 0u : ~0u)) | ((ehi & (ehi - 1)) & (nhi ? 0u : ~0u));
-            needl = needl | mmb_inverse_ballot(bad | tiny | (tie ? ~0ull : 0ull));
+            if (!CHECKED) live = live && pos;
           }
         }
       }
-      if constexpr (POSTHOC) {
+      if constexpr (CHECKED) {
+        return false;
+      } else {
         // What the optimistic choices could get wrong, checked once after the loop:
         // * a pivot outside the in-range square root's domain [2^-700, 2^700] -- a tiny or zero
         //   maximum, a huge or +inf one, a positive NaN key (it would have been the maximum);
@@ -867,7 +625,7 @@ struct Smp {
         //   the chain has more done lanes than steps that took pivots (pe values 0..max_pe, each
         //   taken once when exact: done == max_pe + 1).
         // On a tie the rows the pass computed after it are garbage; the redo replaces them.
-        if constexpr (DW) done = work == inf_s;
+        done = work == inf_s;
         const bool inr = apiv >= 0x1p-700 && apiv <= 0x1p700;
         uint64_t need = __ballot(inb && (done ? !inr : isnan(diag0 - work)));
         const uint64_t dn = __ballot(done && inb);
@@ -876,171 +634,25 @@ struct Smp {
         const int m0 = __builtin_amdgcn_readlane(mpe, 0), m1 = __builtin_amdgcn_readlane(mpe, 32);
         if ((uint32_t)act != 0u && __builtin_popcount((uint32_t)dn) != m0 + 1) need |= 1ull;
         if ((act >> 32) != 0u && __builtin_popcount((uint32_t)(dn >> 32)) != m1 + 1) need |= 1ull << 32;
-        needm = need;
-      } else {
-        needm |= __ballot(needl);
+        return need != 0;
       }
-      return needm != 0;
     };
-#if defined(MMB_PCHOL_ONECOPY)
-    // one copy of the pass, run once optimistically and, rarely, again checked
-#pragma nounroll
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      int ck = attempt;
-      asm volatile("" : "+s"(ck));  // opaque: no peeled second copy
-      if (ck) {  // rare: redo with dpstf2's exact decisions
-        work = inb ? 0.0 : __builtin_inf();
+    // rare (a few per thousand factorizations): redo with dpstf2's exact decisions, the same
+    // unrolled steps inline (an out-of-line redo and a compact-loop redo were both measured
+    // slower: the call forces the live factor rows through scratch); marked unlikely so the
+    // block placement moves the checked pass out of the hot code
+    if (__builtin_expect(pass(mmb_bc<false>{}), 0)) {
+      if (redo_out) *redo_out = 1;
+      work = inb ? 0.0 : __builtin_inf();
 #pragma unroll
-        for (int k = 0; k < DMAX; ++k) Lrow[k] = 0.0;
-        done = !inb;
-        pe = 0;
-        live = true;
-      }
-      if (!pass(ck != 0) || ck) break;
-    }
-#else
-    if constexpr (OPT) {
-#if defined(MMB_EXP_FORCEFAST) || defined(MMB_EXP_NOREDO)
-      (void)pass(mmb_bc<false>{});  // timing experiments only: the optimistic pass alone
-#elif defined(MMB_PCHOL_EXACT_NOINLINE)
-      if (pass(mmb_bc<false>{}))    // rare: redo with dpstf2's exact decisions, out of line
-        return pchol32_exact(d, mat, prow, pks, pos_out, NB, seed, xepoch, c, chain, it, b, m);
-#elif defined(MMB_PCHOL_COMPACT_REDO)
-      if (pass(mmb_bc<false>{})) {  // rare: redo with dpstf2's exact decisions, compact loop
-        redo_exact(d, mat, prow, pks, diag0, lc, inb, Lrow, work, done, pe);
-      }
-#else
-      // rare (a few per thousand factorizations): redo with dpstf2's exact decisions; marked
-      // unlikely so the block placement moves the checked pass out of the hot code
-      if (__builtin_expect(pass(mmb_bc<false>{}), 0)) {
-        if (redo_out) *redo_out = 1;
-        work = inb ? 0.0 : __builtin_inf();
-#pragma unroll
-        for (int k = 0; k < DMAX; ++k) Lrow[k] = 0.0;
-        done = !inb;
-        pe = 0;
-        live = true;
-        (void)pass(mmb_bc<true>{});
-      }
-#endif
-    } else {
+      for (int k = 0; k < DMAX; ++k) Lrow[k] = 0.0;
+      done = !inb;
+      pe = 0;
+      live = true;
       (void)pass(mmb_bc<true>{});
     }
-#endif
-    {
-      const uint64_t dn = __ballot(done && inb);
-      rank = __builtin_popcount(hi_half ? (uint32_t)(dn >> 32) : (uint32_t)dn);
-#ifdef MMB_PCHOL_STEPCHECK
-      // (an optimistic stop at step 0 of a 32-element block has no done / out-of-range lane to
-      // take the garbage pivot: it marked one live lane)
-      if (!live && d == G && rank == 1) rank = 0;
-#endif
-    }
-#else
-#pragma unroll
-    for (int j = 0; j < DMAX; ++j) {
-      if (live && j < d) {
-        const double dl = diag0 - work;
-        // sqrt / reciprocal of the candidate (the compiler keeps them on the pivot lane's
-        // path); out of the fast range the pivot lane takes sqrt() and division instead
-#ifdef MMB_EXP_RCP_SEQ
-        double ajj_s = mmb_sqrt_inrange(dl);
-        double rinv_s = mmb_rcp_inrange(ajj_s);
-#else
-        double ajj_s, rinv_s;
-        mmb_sqrt_rcp_inrange(dl, &ajj_s, &rinv_s);
-#endif
-#ifdef MMB_EXP_PIN_SQRT
-        // timing experiment: keep both sequences ahead of the search (the compiler otherwise
-        // sinks them into the pivot lane's branch); measured 1 % slower
-        asm volatile("" : "+v"(ajj_s), "+v"(rinv_s));
-#endif
-        // key: high word of a positive candidate, INT_MAX for a NaN candidate, else -1
-        // (three independent selects: no branchy nest for the compiler to serialise)
-        const int hiw = (int)(mmb_d2u(dl) >> 32);
-        int key = dl > 0.0 ? hiw : -1;
-        key = isnan(dl) ? 0x7fffffff : key;
-        key = done ? -1 : key;
-        const int mx = gmax_i32(key);
-        const uint32_t win = (uint32_t)(__ballot(key == mx) >> (threadIdx.x & 32));
-        int p = __builtin_ctz(win | 0x80000000u);
-        bool pos = mx >= 0;
-        if (!(mx < 0 || (mx != 0x7fffffff && __builtin_popcount(win) == 1))) {
-          double val;
-          p = pivot_exact(dl, done, pks, j, d, (int*)prow, &val);
-          pos = val > 0.0;
-        }
-        if (!pos) {
-          rank = j;
-          live = false;
-        } else {
-          pks[j] = p;  // same value from every lane of the group: no exec-mask change
-          const bool piv = lane == p;
-          double ajj = 0.0;
-          if (piv) {
-            if (j + 1 < d) {  // the last step has no rows left to update: no readers
-#pragma unroll
-              for (int k = 0; k + 1 < j; k += 2) *(double2*)(prow + k) = make_double2(Lrow[k], Lrow[k + 1]);
-              if (j & 1) prow[j - 1] = Lrow[j - 1];
-            }
-            ajj = ajj_s;  // IEEE results in the fast range (device.h)
-            double rinv = rinv_s;
-            if (!mmb_fast_range(dl)) {
-              ajj = sqrt(dl);
-              rinv = 1.0 / ajj;
-            }
-            prow[RI] = rinv;
-          }
-          grp_sync();
-          if (piv) { Lrow[j] = ajj; pe = j; }
-          done = done || piv;
-#ifndef MMB_EXP_LDS_DOT
-          // pivot row: lane l of each 16-lane row reads elements l and 16 + l (two 8-byte reads
-          // instead of j/2 16-byte broadcast reads per lane), then every product takes element k
-          // from lane k % 16 of its row by a DPP64 row_newbcast operand.  Every lane of the group
-          // runs the dot product (a DPP source lane must be active); done lanes discard it.
-          double t0 = 0.0, t1 = 0.0;
-          // Sigma(lane, p) and the pivot's reciprocal are read with the row pieces (one LDS wait)
-          // Sigma(lc, p) at byte 8 slot = 4 a (a + 1) + 8 b, a = max, b = min: max, min, one
-          // 24-bit multiply-add and two shift-adds
-          const int sa = max(lc, p), sb = min(lc, p);
-          int sq;  // sa (sa + 1) in one instruction (the compiler splits it into three)
-          asm("v_mad_u32_u24 %0, %1, %1, %1" : "=v"(sq) : "v"(sa));
-          double sig = *(const double*)((const char*)mat + ((sq + 2 * sb) << 2));
-          double rinv = prow[RI];
-          double pA = prow[lane & 15];
-          double pB = j > 16 ? prow[16 + (lane & 15)] : 0.0;
-          asm volatile("" : "+v"(sig), "+v"(rinv), "+v"(pA), "+v"(pB));
-          if (j > 0 && j + 1 < d) {  // (j = d - 1: every lane is done)
-#pragma unroll
-            for (int k = 0; k < j; ++k) {
-              const double src = k < 16 ? pA : pB;
-              if (k & 1) fmac_rowbc_ld(t1, src, Lrow[k], k & 15);
-              else fmac_rowbc_ld(t0, src, Lrow[k], k & 15);
-            }
-          }
-#endif
-          if (!done) {
-#ifdef MMB_EXP_LDS_DOT
-            double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-            for (int k = 0; k + 1 < j; k += 2) {
-              const double2 pp = *(const double2*)(prow + k);
-              t0 = fma(Lrow[k], pp.x, t0);
-              t1 = fma(Lrow[k + 1], pp.y, t1);
-            }
-            if (j & 1) t0 = fma(Lrow[j - 1], prow[j - 1], t0);
-            const double sig = mat[mmb_slot(lane, p)], rinv = prow[RI];
-#endif
-            const double lij = (sig - (t0 + t1)) * rinv;
-            Lrow[j] = lij;
-            work = work + lij * lij;
-          }
-          grp_sync();
-        }
-      }
-    }
-#endif  // MMB_PCHOL_V1
+    const uint64_t dn = __ballot(done && inb);
+    rank = __builtin_popcount(hi_half ? (uint32_t)(dn >> 32) : (uint32_t)dn);  // pivots taken
     return tail();
   }
 
@@ -1303,24 +915,17 @@ struct Smp {
       double* const mat_l = mat + g.lane;
       auto slots = [&](auto fresh_c) {
         constexpr bool FRESH = decltype(fresh_c)::value;
-#ifndef MMB_EXP_IK_PERSLOT
         // opaque once per update: the table reads can be issued together (one LDS wait), but
         // not hoisted out of the iteration loop (2 * NT ints live across it: spills)
         int li0 = g.lane;
         asm volatile("" : "+v"(li0));
-#endif
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
           const int t = u * G + g.lane;
           if ((u + 1) * G <= TP || t < TP) {
             int i, k;
             if constexpr (IKTAB) {
-#ifdef MMB_EXP_IK_PERSLOT
-              int li = g.lane;
-              asm volatile("" : "+v"(li));
-#else
               const int li = li0;
-#endif
               const int w = ik_table()[li + u * G];
               i = w >> 8;
               k = w & 255;
@@ -1356,20 +961,14 @@ struct Smp {
       int* pks = (int*)z2s;  // pivot order (group-uniform values), LDS
       grp_sync();
       MMB_PROF_MARK(4, g.lane)
-#ifdef MMB_EXP_NOPCHOL
-      int rank = d;  // timing experiment only
-#else
       int rank;
       int redo = 0;
       const bool carry = CARRY && B.t_xtag != nullptr && B.sigl_diag;
-#ifndef MMB_PCHOL_GENERIC
       int pe = 0;
       if constexpr (G == 32 && R == 1)
         rank = pchol32(d, mat, (double*)ia, pks, g, &pe, carry ? &B : nullptr, A, c, chain, it, b, m, &redo);
       else
-#endif
         rank = pchol(d, mat, (double*)ia, pks, g);
-#endif
       grp_sync();
       MMB_PROF_MARK(5, g.lane)
       if (B.t_astat != nullptr) amm_count(B, c, d, rank, redo, g);
@@ -1448,11 +1047,7 @@ struct Smp {
     M::unlist(B, s, g.lane, x);
     typename M::SCtx cx;
     M::slice_cand_prep(A, B, s, l, g, lds, cx);
-#ifndef MMB_EXP_SLICE_LOGF  // (experiment: logf recomputing every sum)
     double logf0 = M::slice_logf0(A, B, s, l, g, x, cx);  // logf, reusing the prep's sums
-#else
-    double logf0 = M::logf(A, B, s, l, g, x);
-#endif
     double lo = 0.0, up = 0.0;
     if (g.lane < d) {
       const double w = width(B, g.lane);
@@ -1589,11 +1184,7 @@ struct Smp {
     UWin uw{0.0, 0xffffffffu - (uint32_t)G};
     typename M::SCtx cx;
     M::slice_cand_prep(A, B, s, l, g, lds, cx);
-#ifndef MMB_EXP_SLICE_LOGF
     const double p0 = M::slice_logf0(A, B, s, l, g, v, cx) + mmb_log(uwin_next(ru, uw, 0u, g));
-#else
-    const double p0 = M::logf(A, B, s, l, g, v) + mmb_log(uwin_next(ru, uw, 0u, g));
-#endif
     typename M::SMemo memo;
     double vu[SD], lo[SD], up[SD], x1[SD];
 #pragma unroll
