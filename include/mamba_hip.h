@@ -348,6 +348,13 @@ int mmb_order_hist(mmb_engine* e, int param, int ntargets, const uint64_t* prefi
 
 /* Timing / sync (bench.py roofline) */
 int mmb_sync(mmb_engine* e);
+/* Device time of the last mmb_run window's kernel launches (time_kernels nonzero).  A sweep window
+ * may run as chain parts on streams of their own, whose launches overlap (MMB_SWEEP_PARTS):
+ * total_ms is the time during which at least one sweep launch of the window was in flight -- the
+ * union of the launches' [start, end] intervals, not their sum -- so it never exceeds the window's
+ * wall time; with one part that is the sum as before.  launches counts every part's launches;
+ * units (chain-updates) does not depend on the parts.  (Logistic windows: the summed
+ * gradient-kernel time of their parts.) */
 int mmb_kernel_time(const mmb_engine* e, double* total_ms, int64_t* launches, int64_t* units);
 int mmb_state_bytes(const mmb_engine* e, double* bytes_per_chain_update);
 /* Gradient evaluations (logpdf!+gradlogpdf! calls, sampler.jl:97-119) in the last mmb_run,

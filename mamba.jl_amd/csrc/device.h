@@ -148,6 +148,8 @@ struct SweepArgs {
   int32_t ir_amm;        // AMM scratch doubles at the start of a chain's LDS (0 without AMM)
   int32_t ir_lds;        // LDS doubles per chain
   const int32_t* cperm;  // lane-group slot -> chain (null: identity), sweep.hip order_chains_kernel
+  int32_t wg_offset;     // chain parts (engine.cpp mmb_run): workgroup b of this launch is workgroup
+  int32_t wg_stride;     // b * wg_stride + wg_offset of the shard (0, 1: the launch holds every workgroup)
   int32_t amwg_exact;    // MMB_AMWG_EXACT: 1 = AMWG takes amwg_sub!'s sequential loop (samplers.h amwg),
                          // 2 = AMWG certainty band widened 2^30 times (tests: frequent fallback)
   int32_t slice_exact;   // MMB_SLICE_EXACT=1: Slice evaluates one shrink candidate at a time (slice_uni /

@@ -40,7 +40,13 @@ hipError_t mmb_launch_order_hist(int P, int j, int64_t n, int K, const double* d
 hipError_t mmb_launch_gr_stats(int pmon, int64_t n, int K, const double* draws, const int32_t* link,
                                const double* shift, double* stats, hipStream_t st);
 
+hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
+
 static thread_local std::string g_last_error;
+
+// chain parts of a sweep window (mmb_run): the engine stream and three more, as many streams as a
+// process has hardware queues by default (streams that share a queue serialise)
+constexpr int MMB_SWEEP_PARTS_MAX = 4;
 
 struct BlockHost {
   mmb_block_spec spec;
@@ -93,6 +99,11 @@ struct mmb_engine {
   std::vector<hipEvent_t> evpoolx[MMB_LG_SPLIT_MAX - 1];  // kernel timing events of parts 1..
   int64_t lg_steps = 0;  // gradient steps of the last window
   unsigned long long* lg_ngrad = nullptr;
+  // sweep parts (mmb_run): the streams of parts 1.. (part 0: the engine stream), created on first use
+  hipStream_t sw_streamx[MMB_SWEEP_PARTS_MAX - 1] = {};
+  hipEvent_t sw_join[MMB_SWEEP_PARTS_MAX] = {};           // [0] fork, [i] join of part i
+  std::vector<hipEvent_t> sw_evpoolx[MMB_SWEEP_PARTS_MAX - 1];  // kernel timing events of parts 1..
+  int sw_resident = 0;  // workgroups of the sweep kernel the device holds at once (0: not asked yet)
   int32_t* d_cperm = nullptr;  // lane-group slot -> chain of the 32-lane sweep kernels (order_chains)
   bool cperm_identity = true;
   bool order_fresh = false;    // d_cperm holds a table computed after a window (a host write of the
@@ -847,6 +858,7 @@ void mmb_prof_dump_line();
 #endif
 #ifdef MMB_WAVE_TIMES
 void mmb_wave_times_dump(int nwaves, int slots);
+void mmb_wave_times_reset(hipStream_t st);
 #endif
 
 void mmb_destroy(mmb_engine* e) {
@@ -854,7 +866,9 @@ void mmb_destroy(mmb_engine* e) {
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
 #ifdef MMB_WAVE_TIMES
-  if (e->model == MMB_MODEL_RATS) mmb_wave_times_dump((int)((e->K + 1) / 2), 4096);
+  // rats: two chains per wave, four waves per workgroup
+  if (e->model == MMB_MODEL_RATS)
+    mmb_wave_times_dump((int)((e->K + 1) / 2), e->sw_resident > 0 ? 4 * e->sw_resident : 4096);
 #endif
   if (e->jit_mod && std::getenv("MMB_IR_JIT_PROF") && std::atoi(std::getenv("MMB_IR_JIT_PROF")) == 1) {
     // phase timers of a profiling specialised kernel (ir_jit.cpp): the static kernels' names
@@ -892,6 +906,12 @@ void mmb_destroy(mmb_engine* e) {
   for (auto& pool : e->evpoolx)
     for (hipEvent_t ev : pool) (void)hipEventDestroy(ev);
   for (hipStream_t q : e->lg_streamx)
+    if (q) (void)hipStreamDestroy(q);
+  for (hipEvent_t ev : e->sw_join)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& pool : e->sw_evpoolx)
+    for (hipEvent_t ev : pool) (void)hipEventDestroy(ev);
+  for (hipStream_t q : e->sw_streamx)
     if (q) (void)hipStreamDestroy(q);
   if (e->ev0) (void)hipEventDestroy(e->ev0);
   if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1208,6 +1228,8 @@ static void fill_args(const mmb_engine* e, SweepArgs& A) {
   A.ig_c = 0.001 * std::log(0.001) - std::lgamma(0.001);
   A.blocks = e->d_blocks;
   A.cperm = e->cperm_identity ? nullptr : e->d_cperm;
+  A.wg_offset = 0;  // one part: every workgroup (mmb_run deals them to parts)
+  A.wg_stride = 1;
   {  // MMB_AMWG_EXACT=1: AMWG updates by amwg_sub!'s sequential loop; 2: wide AMWG band.
      // MMB_SLICE_EXACT=1: Slice shrink candidates one at a time.  MMB_AMWG_PROBE=1: tests only.
     const char* ae = std::getenv("MMB_AMWG_EXACT");
@@ -1241,14 +1263,69 @@ static void fill_args(const mmb_engine* e, SweepArgs& A) {
   }
 }
 
-static int iters_per_launch(const mmb_engine* e) {
-  const char* s = std::getenv("MMB_ITERS_PER_LAUNCH");
-  if (s && std::atoi(s) > 0) return std::atoi(s);
+// Chain parts of a window (mmb_run).  A launch of the rats kernels ends in a tail: its wavefronts
+// fall into duration classes, two per resident slot, and the slots that drew the short ones idle
+// until the last wave is done (busy 84-86 % of a launch's span), and the next
+// launch waits on the stream for that last wave although it depends on its own chains only.  So the
+// workgroups are dealt round-robin to `parts` parts over the one sorted slot -> chain table (the
+// same class mix in each, slow classes first), every part a sequence of launches on its own
+// stream: a part's launch n + 1 waits for its own launch n, and the other parts' resident launches
+// fill the slots its tail frees.  Results do not depend on the parts (every index of the kernel
+// is the chain's own).  The 32-lane kernels only (rats and the node IR; the line and logistic paths
+// have no parts): MMB_SWEEP_PARTS=1..4 forces the count; unset, MMB_SWEEP_PARTS_DEFAULT parts when
+// each part still has a workgroup for every resident workgroup slot of the device, else one.
+// Default 2 (16384 rats chains, 400 steps: 1.45-1.46e8 chain-updates/s vs 1.32-1.33e8 on one
+// stream; 3 parts as fast, 4 slower than one).
+constexpr int MMB_SWEEP_PARTS_DEFAULT = 2;
+static int sweep_parts(mmb_engine* e, const SweepArgs& A, int* parts) {
+  *parts = 1;
+  if (!(e->model == MMB_MODEL_RATS || e->model == MMB_MODEL_IR)) return 0;
+  int nwg = 0, per_cu = 0;
+  if (e->jit_fn) {  // specialised node-IR kernel: the interpreter's launch shape (mmb_run)
+    const int per_block = 128 / Mdl<MMB_MODEL_IR>::G;
+    nwg = (A.K + per_block - 1) / per_block;
+    if (!e->sw_resident) {
+      const size_t lds = (size_t)per_block * Mdl<MMB_MODEL_IR>::lds_stride(A) * sizeof(double);
+      HIPCHK(e, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, e->jit_fn, 128, lds));
+    }
+  } else {
+    hipError_t st = mmb_sweep_shape(e->model, e->kinds, A, &nwg, e->sw_resident ? nullptr : &per_cu);
+    if (st != hipSuccess) return fail(e, MMB_E_HIP, "sweep shape: %s", hipGetErrorString(st));
+  }
+  if (!e->sw_resident) {
+    int cus = 0;
+    HIPCHK(e, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
+    e->sw_resident = std::max(1, per_cu * cus);
+  }
+  int p = 1;
+  const char* s = std::getenv("MMB_SWEEP_PARTS");
+  if (s && std::atoi(s) >= 1) {
+    p = std::min(std::atoi(s), MMB_SWEEP_PARTS_MAX);
+  } else {
+    p = MMB_SWEEP_PARTS_DEFAULT;
+    while (p > 1 && nwg / p < e->sw_resident) --p;
+  }
+  *parts = std::max(1, std::min(p, nwg));  // a part past the last workgroup would launch nothing
+  return 0;
+}
+
+static int iters_per_launch_one(const mmb_engine* e) {
   // rats: 20 (16384 chains: ~2.5 ms launches; 16 was 0.5-0.9 % over 8 and 6 % over 4 in the
   // round-4 A/B, the launch tail amortised; round 5: 20 as fast as 16 and 32 over 400 steps, and a
   // 20-iteration window runs as one launch: 1.226e8 vs 1.21e8 for 10 + 10); line: 256 (an
   // iteration of the quad kernel is ~8 us, so 64 per launch left a launch gap every ~0.5 ms)
   return e->model == MMB_MODEL_RATS ? 20 : e->model == MMB_MODEL_IR ? 16 : e->model == MMB_MODEL_LINE ? 256 : 64;
+}
+
+static int iters_per_launch(const mmb_engine* e, int parts, int64_t iters) {
+  const char* s = std::getenv("MMB_ITERS_PER_LAUNCH");
+  if (s && std::atoi(s) > 0) return std::atoi(s);
+  const int W = iters_per_launch_one(e);
+  // chain parts fill each other's launch tails only from a part's second launch on (all parts'
+  // first launches start together), so a window that would be a single launch runs as two:
+  // 16384 rats chains, 20 iterations, 2 parts: 10 + 10 1.25-1.28e8 chain-updates/s, 20 1.21e8
+  if (parts > 1 && iters > 1) return (int)std::min<int64_t>(W, (iters + 1) / 2);
+  return W;
 }
 
 template <class T>
@@ -1554,38 +1631,86 @@ int mmb_run(mmb_engine* e, const mmb_run_args* a) {
   A.model_burnin = a->model_burnin;
   A.kept_origin = kept0;
   A.draws = (want && nk > 0) ? e->d_draws : nullptr;
-  const int W = iters_per_launch(e);
+  int np = 1;
+  {
+    int rc = sweep_parts(e, A, &np);
+    if (rc) return rc;
+  }
+  const int W = iters_per_launch(e, np, a->iters);
   e->kernel_ms = 0.0;
   e->launches = 0;
   e->units = 0;
-  const int64_t nl = (a->iters + W - 1) / W;
-  if (a->time_kernels) {
-    while ((int64_t)e->evpool.size() < 2 * nl) {
-      hipEvent_t ev;
-      HIPCHK(e, hipEventCreate(&ev));
-      e->evpool.push_back(ev);
+  const int64_t nl = a->iters > 0 ? (a->iters + W - 1) / W : 0;
+  hipStream_t pst[MMB_SWEEP_PARTS_MAX];
+  std::vector<hipEvent_t>* pev[MMB_SWEEP_PARTS_MAX];
+  for (int p = 0; p < np; ++p) {
+    if (p > 0 && !e->sw_streamx[p - 1])
+      HIPCHK(e, hipStreamCreateWithFlags(&e->sw_streamx[p - 1], hipStreamNonBlocking));
+    pst[p] = p == 0 ? e->stream : e->sw_streamx[p - 1];
+    pev[p] = p == 0 ? &e->evpool : &e->sw_evpoolx[p - 1];
+    if (a->time_kernels) {
+      while ((int64_t)pev[p]->size() < 2 * nl) {
+        hipEvent_t ev;
+        HIPCHK(e, hipEventCreate(&ev));
+        pev[p]->push_back(ev);
+      }
     }
+  }
+  if (np > 1)
+    for (int p = 0; p < np; ++p)
+      if (!e->sw_join[p]) HIPCHK(e, hipEventCreateWithFlags(&e->sw_join[p], hipEventDisableTiming));
+  // every return from here on -- the error paths included -- leaves no part kernel running: the
+  // engine stream alone orders whatever the caller does next
+  struct PartDrain {
+    hipStream_t* st;
+    int n;
+    bool armed = true;
+    ~PartDrain() {
+      if (armed)
+        for (int p = 1; p < n; ++p) (void)hipStreamSynchronize(st[p]);
+    }
+  } drain{pst, np};
+#ifdef MMB_WAVE_TIMES
+  if (nl > 0) mmb_wave_times_reset(e->stream);
+#endif
+  if (np > 1 && nl > 0) {  // fork: the part streams start behind everything queued on the engine stream
+    HIPCHK(e, hipEventRecord(e->sw_join[0], e->stream));
+    for (int p = 1; p < np; ++p) HIPCHK(e, hipStreamWaitEvent(pst[p], e->sw_join[0], 0));
   }
   for (int64_t done = 0, li = 0, w = 0; done < a->iters; done += w, ++li) {
     w = launch_width(a->iters, W, li);
     A.iter0 = it0 + done;
     A.n_iters = w;
-    if (a->time_kernels) HIPCHK(e, hipEventRecord(e->evpool[2 * li], e->stream));
-    hipError_t st;
-    if (e->jit_fn) {  // node IR, specialised kernel: the interpreter's launch shape (4 chains / 128 threads)
-      const int per_block = 128 / Mdl<MMB_MODEL_IR>::G;
-      const unsigned grid = (unsigned)((A.K + per_block - 1) / per_block);
-      const size_t lds = (size_t)per_block * Mdl<MMB_MODEL_IR>::lds_stride(A) * sizeof(double);
-      void* args[] = {(void*)&A};
-      st = hipModuleLaunchKernel(e->jit_fn, grid, 1, 1, 128, 1, 1, (unsigned)lds, e->stream, args, nullptr);
-    } else {
-      st = mmb_launch_sweep(e->model, e->kinds, A, e->stream);
+    // launch li of every part: part p holds workgroups p, p + np, ... of the one slot -> chain
+    // table (the same class mix in every part), and its launch li + 1 waits for its own launch li only
+    for (int p = 0; p < np; ++p) {
+      A.wg_offset = p;
+      A.wg_stride = np;
+      if (a->time_kernels) HIPCHK(e, hipEventRecord((*pev[p])[2 * li], pst[p]));
+      hipError_t st;
+      if (e->jit_fn) {  // node IR, specialised kernel: the interpreter's launch shape (4 chains / 128 threads)
+        const int per_block = 128 / Mdl<MMB_MODEL_IR>::G;
+        const int nwg = (A.K + per_block - 1) / per_block;
+        const unsigned grid = (unsigned)((nwg - p + np - 1) / np);
+        const size_t lds = (size_t)per_block * Mdl<MMB_MODEL_IR>::lds_stride(A) * sizeof(double);
+        void* args[] = {(void*)&A};
+        st = hipModuleLaunchKernel(e->jit_fn, grid, 1, 1, 128, 1, 1, (unsigned)lds, pst[p], args, nullptr);
+      } else {
+        st = mmb_launch_sweep(e->model, e->kinds, A, pst[p]);
+      }
+      if (st != hipSuccess) return fail(e, MMB_E_HIP, "sweep launch: %s", hipGetErrorString(st));
+      if (a->time_kernels) HIPCHK(e, hipEventRecord((*pev[p])[2 * li + 1], pst[p]));
+      e->launches += 1;
     }
-    if (st != hipSuccess) return fail(e, MMB_E_HIP, "sweep launch: %s", hipGetErrorString(st));
-    if (a->time_kernels) HIPCHK(e, hipEventRecord(e->evpool[2 * li + 1], e->stream));
-    e->launches += 1;
     e->units += (int64_t)w * e->K;
   }
+  if (np > 1 && nl > 0) {  // join: later work on the engine stream sees every part's results
+    for (int p = 1; p < np; ++p) {
+      HIPCHK(e, hipEventRecord(e->sw_join[p], pst[p]));
+      HIPCHK(e, hipStreamWaitEvent(e->stream, e->sw_join[p], 0));
+    }
+  }
+  drain.armed = false;  // joined: the engine stream orders everything after the parts
   if (a->iters > 0 && (!e->order_fresh || it0 + a->iters - e->order_iter >= order_every())) {
     // the next window's order from this window's final flags, queued behind its last launch so
     // it runs while the host is between windows (a host write of the tune state invalidates it).
@@ -1598,12 +1723,33 @@ int mmb_run(mmb_engine* e, const mmb_run_args* a) {
     e->order_fresh = true;
     e->order_iter = it0 + a->iters;
   }
-  if (a->time_kernels) {  // per-launch device time, summed after the window (no per-launch sync)
-    HIPCHK(e, hipEventSynchronize(e->evpool[2 * nl - 1]));
-    for (int64_t li = 0; li < nl; ++li) {
-      float ms = 0.f;
-      HIPCHK(e, hipEventElapsedTime(&ms, e->evpool[2 * li], e->evpool[2 * li + 1]));
-      e->kernel_ms += ms;
+  if (a->time_kernels && nl > 0) {
+    // device time of the window's launches, read after the window (no per-launch sync): the time
+    // during which at least one launch was in flight.  One part's launches follow each other on
+    // their stream, so that is their sum; launches of different parts overlap (their sum could
+    // exceed the wall time), so it is the union of the [start, end] intervals on the clock of the
+    // window's first event.
+    std::vector<std::pair<float, float>> iv;
+    for (int p = 0; p < np; ++p) {
+      HIPCHK(e, hipEventSynchronize((*pev[p])[2 * nl - 1]));
+      for (int64_t li = 0; li < nl; ++li) {
+        float t0 = 0.f, dt = 0.f;
+        HIPCHK(e, hipEventElapsedTime(&dt, (*pev[p])[2 * li], (*pev[p])[2 * li + 1]));
+        if (np == 1) {
+          e->kernel_ms += dt;
+          continue;
+        }
+        if (p > 0 || li > 0) HIPCHK(e, hipEventElapsedTime(&t0, (*pev[0])[0], (*pev[p])[2 * li]));
+        iv.emplace_back(t0, t0 + dt);
+      }
+    }
+    std::sort(iv.begin(), iv.end());
+    for (size_t i = 0; i < iv.size();) {
+      float hi = iv[i].second;
+      size_t j = i + 1;
+      for (; j < iv.size() && iv[j].first <= hi; ++j) hi = std::max(hi, iv[j].second);
+      e->kernel_ms += hi - iv[i].first;
+      i = j;
     }
   }
   e->iter = it0 + a->iters;

@@ -16,10 +16,11 @@
 extern __device__ unsigned long long mmb_prof[32];
 #endif
 #ifdef MMB_WAVE_TIMES
-// diagnostics: per wave of the last launch, its start and end on the 100 MHz constant clock
-// (engine.cpp dumps the occupancy summary at mmb_destroy)
+// diagnostics: per wave slot of the shard, over the launches of the last mmb_run window (all
+// parts): first start, last end and summed residency on the 100 MHz constant clock (engine.cpp
+// clears them before a window and dumps the occupancy summary at mmb_destroy)
 #define MMB_WT_MAX 65536
-extern __device__ unsigned long long mmb_wt[2 * MMB_WT_MAX];
+extern __device__ unsigned long long mmb_wt[3 * MMB_WT_MAX];
 #endif
 
 #ifndef MMB_SWEEP_WAVES
@@ -55,10 +56,13 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
     __syncthreads();
   }
 #endif
-  const int slot = (int)((blockIdx.x * blockDim.x + threadIdx.x) / G);
+  // workgroup of the shard: the engine may run the shard as parts, each a launch of its own that
+  // holds every wg_stride-th workgroup (engine.cpp mmb_run); offset 0, stride 1: all of them
+  const unsigned wg = blockIdx.x * (unsigned)A.wg_stride + (unsigned)A.wg_offset;
+  const int slot = (int)((wg * blockDim.x + threadIdx.x) / G);
 #ifdef MMB_WAVE_TIMES
   const uint64_t _wt0 = __builtin_amdgcn_s_memrealtime();
-  const int _wid = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const int _wid = (int)((wg * blockDim.x + threadIdx.x) >> 6);  // the wave's slot in the shard, not the launch
 #endif
   if (slot >= A.K) return;  // whole lane groups exit together
   // chain of this lane group: the engine may order the chains so that chains whose pivoted
@@ -147,9 +151,11 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
   }
   M::store(A, c, g.lane, s);
 #ifdef MMB_WAVE_TIMES
-  if ((threadIdx.x & 63) == 0 && _wid < MMB_WT_MAX) {
-    mmb_wt[2 * _wid] = _wt0;
-    mmb_wt[2 * _wid + 1] = __builtin_amdgcn_s_memrealtime();
+  if ((threadIdx.x & 63) == 0 && _wid < MMB_WT_MAX) {  // (a wave slot's launches follow each other: no race)
+    const uint64_t _wt1 = __builtin_amdgcn_s_memrealtime();
+    if (mmb_wt[3 * _wid] == 0) mmb_wt[3 * _wid] = _wt0;
+    mmb_wt[3 * _wid + 1] = _wt1;
+    mmb_wt[3 * _wid + 2] += _wt1 - _wt0;
   }
 #endif
 #ifdef MMB_PHASE_PROF

@@ -20,48 +20,59 @@ void mmb_prof_dump() {
 #include <algorithm>
 #include <cstdio>
 #include <vector>
-__device__ unsigned long long mmb_wt[2 * MMB_WT_MAX];
-// occupancy of the last sweep launch: span, summed wave residency, the fraction of the resident
-// slots' time the waves filled, and when the waves ended (deciles of the span)
+__device__ unsigned long long mmb_wt[3 * MMB_WT_MAX];
+void mmb_wave_times_reset(hipStream_t st) {
+  void* p = nullptr;
+  if (hipGetSymbolAddress(&p, HIP_SYMBOL(mmb_wt)) == hipSuccess)
+    (void)hipMemsetAsync(p, 0, sizeof(unsigned long long) * 3 * MMB_WT_MAX, st);
+}
+// occupancy of the last window's sweep launches, all parts: the window's span (first wave start
+// to last wave end), the summed wave residency, and the fraction of the resident slots' time
+// over that span which the waves filled
 void mmb_wave_times_dump(int nwaves, int slots) {
-  std::vector<unsigned long long> h(2 * MMB_WT_MAX);
+  std::vector<unsigned long long> h(3 * MMB_WT_MAX);
   if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(mmb_wt), h.size() * sizeof(unsigned long long)) != hipSuccess) return;
   nwaves = std::min(nwaves, MMB_WT_MAX);
   unsigned long long t0 = ~0ull, t1 = 0;
   double busy = 0.0;
   int n = 0;
   for (int w = 0; w < nwaves; ++w) {
-    if (h[2 * w] == 0 || h[2 * w + 1] < h[2 * w]) continue;
-    t0 = std::min(t0, h[2 * w]);
-    t1 = std::max(t1, h[2 * w + 1]);
-    busy += (double)(h[2 * w + 1] - h[2 * w]);
+    if (h[3 * w] == 0 || h[3 * w + 1] < h[3 * w]) continue;
+    t0 = std::min(t0, h[3 * w]);
+    t1 = std::max(t1, h[3 * w + 1]);
+    busy += (double)h[3 * w + 2];
     ++n;
   }
   if (!n) return;
   const double span = (double)(t1 - t0);
-  int dec[10] = {0}, sdec[10] = {0};
-  for (int w = 0; w < nwaves; ++w) {
-    if (h[2 * w] == 0) continue;
-    dec[std::min(9, (int)(10.0 * (double)(h[2 * w + 1] - t0) / span))]++;
-    sdec[std::min(9, (int)(10.0 * (double)(h[2 * w] - t0) / span))]++;
-  }
-  fprintf(stderr, "MMB_WT waves %d span_us %.1f mean_wave_us %.1f fill(slots=%d) %.4f\nMMB_WT end_deciles", n,
+  fprintf(stderr, "MMB_WT window: wave slots %d span_us %.1f busy_per_slot_us %.1f fill(slots=%d) %.4f\n", n,
           span / 100.0, busy / n / 100.0, slots, busy / (span * slots));
-  for (int i = 0; i < 10; ++i) fprintf(stderr, " %d", dec[i]);
-  fprintf(stderr, "\nMMB_WT start_deciles");
-  for (int i = 0; i < 10; ++i) fprintf(stderr, " %d", sdec[i]);
-  fprintf(stderr, "\n");
 }
 #endif
 
+// workgroups of the whole shard; a launch holds those of its part (SweepArgs wg_offset, wg_stride)
 template <int MODEL, unsigned KINDS>
 static hipError_t launch(const SweepArgs& A, hipStream_t st, int threads) {
   using M = Mdl<MODEL>;
   const int per_block = threads / M::G;
-  const int blocks = (A.K + per_block - 1) / per_block;
+  const int nwg = (A.K + per_block - 1) / per_block;
+  if (A.wg_stride < 1 || A.wg_offset < 0 || A.wg_offset >= A.wg_stride) return hipErrorInvalidValue;
+  const int blocks = (nwg - A.wg_offset + A.wg_stride - 1) / A.wg_stride;
+  if (blocks <= 0) return hipSuccess;  // a part past the last workgroup
   const size_t lds = (size_t)per_block * M::lds_stride(A) * sizeof(double);
   hipLaunchKernelGGL((sweep_kernel<MODEL, KINDS>), dim3(blocks), dim3(threads), lds, st, A);
   return hipGetLastError();
+}
+
+// launch shape of the shard: its workgroups and (wg_per_cu non-null) how many of them a CU holds at once
+template <int MODEL, unsigned KINDS>
+static hipError_t shape(const SweepArgs& A, int threads, int* nwg, int* wg_per_cu) {
+  using M = Mdl<MODEL>;
+  const int per_block = threads / M::G;
+  *nwg = (A.K + per_block - 1) / per_block;
+  if (!wg_per_cu) return hipSuccess;
+  const size_t lds = (size_t)per_block * M::lds_stride(A) * sizeof(double);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg_per_cu, sweep_kernel<MODEL, KINDS>, threads, lds);
 }
 
 // Wavefront pairing (engine.cpp order_chains): the slot -> chain table of the next window as a
@@ -160,5 +171,17 @@ hipError_t mmb_launch_sweep(int model, unsigned kinds, const SweepArgs& A, hipSt
     if (kinds & K_GRAD) return launch<MMB_MODEL_LINE, K_ALL_GRAD>(A, st, 64);
     return launch<MMB_MODEL_LINE, K_ALL>(A, st, 64);
   }
+  return hipErrorInvalidValue;
+}
+
+// the 32-lane kernels' launch shape (engine.cpp sweep_parts); the same dispatch as mmb_launch_sweep
+hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu) {
+  if (model == MMB_MODEL_RATS) {
+    constexpr int TB = MMB_RATS_BLOCK;
+    if ((kinds & ~K_GIBBS_AMM) == 0) return shape<MMB_MODEL_RATS, K_GIBBS_AMM>(A, TB, nwg, wg_per_cu);
+    if ((kinds & ~K_SLICE_AMWG) == 0) return shape<MMB_MODEL_RATS, K_SLICE_AMWG>(A, TB, nwg, wg_per_cu);
+    return shape<MMB_MODEL_RATS, K_ALL>(A, TB, nwg, wg_per_cu);
+  }
+  if (model == MMB_MODEL_IR) return shape<MMB_MODEL_IR, K_IR>(A, 128, nwg, wg_per_cu);
   return hipErrorInvalidValue;
 }
