@@ -346,6 +346,48 @@ int mmb_chain_summary(mmb_engine* e, const double* shift /* p */, int64_t batch_
 int mmb_order_hist(mmb_engine* e, int param, int ntargets, const uint64_t* prefix, int pass,
                    uint64_t* counts /* ntargets x 256 */);
 
+/* Upload draws: the inverse of mmb_get_draws.  `draws` is nkept x p x K column-major (the
+ * Chains value layout, iteration fastest); it is transposed into the device draw buffer, which
+ * grows by mmb_reserve_draws' rule, and becomes the engine's kept window (mmb_num_kept ==
+ * nkept), so every device summary runs on it: a Chains read back from a file, or a series chosen
+ * by a test.  Needs mmb_init_chains and nkept >= 1. */
+int mmb_set_draws(mmb_engine* e, const double* draws, int64_t nkept);
+
+/* Per-chain convergence diagnostics of the device-kept draws (diag.hip): the per-element work of
+ * autocor / changerate (/root/reference/src/output/stats.jl:3-39), gewekediag
+ * (src/output/gewekediag.jl) and mcse (src/output/mcse.jl:3-46), per local chain k and monitored
+ * param j.  Windows are 0-based half-open ranges [i0, i1) of the kept draws, 0 <= i0 < i1 <=
+ * mmb_num_kept, n_w = i1 - i0; outputs are C row-major.  The window mean is taken on x - x[i0] and
+ * every sum of products on z = x - mean, so a series of equal elements gives gamma(l) = 0
+ * exactly (mcse 0; autocorrelation and Geweke z then 0/0 = NaN, as in the reference).
+ * mmb_chain_autocov: out[(k*p + j)*(2 + nlags) + f] = [mean, gamma(0), gamma(lags[0]), ...] with
+ *   gamma(l) = sum_t z_t z_{t+l} / n_w (StatsBase autocov(x, lags; demean=true)), all lags in
+ *   one sweep.  0 <= nlags <= MMB_DIAG_MAX_LAGS, each lag in 1 .. n_w - 1 (else MMB_E_ARG, "lags
+ *   must be less than the sample length").
+ * mmb_chain_mcse: out[(k*p + j)*MMB_MCSE_FIELDS + f] = [mean, gamma(0), mcse, terms].
+ *   MMB_MCSE_IMSE / MMB_MCSE_IPSE follow mcse_imse / mcse_ipse (mcse.jl:21-46) statement for
+ *   statement on the window's series (m = div(n_w - 2, 2), the running min of IMSE, Ghat > 0 ||
+ *   break; n_w >= 2); terms = lag pairs added in the loop.  MMB_MCSE_BM is mcse_bm(x;
+ *   size=batch_size) of the window alone (batches start at i0, the remainder is dropped;
+ *   n_w < 2*batch_size is MMB_E_ARG with the reference's message); terms = batches.
+ *   batch_size is ignored by the other two.
+ *   The one departure from the reference: where `value` is negative its sqrt throws a
+ *   DomainError; a kernel over thousands of chains cannot throw for one of them and writes NaN
+ *   for that (chain, param).
+ * mmb_change_counts: out[j], j < p = the number of (local chain, i >= 1) with x[i] != x[i-1] for
+ *   param j over all kept draws; out[p] = the number with any param changed (stats.jl:19-39).
+ *   Exact integer counts, additive across GPUs. */
+#define MMB_DIAG_MAX_LAGS 16
+#define MMB_MCSE_FIELDS 4
+#define MMB_MCSE_BM 0
+#define MMB_MCSE_IMSE 1
+#define MMB_MCSE_IPSE 2
+int mmb_chain_autocov(mmb_engine* e, int64_t i0, int64_t i1, int nlags, const int64_t* lags,
+                      double* out /* K x p x (2 + nlags) */);
+int mmb_chain_mcse(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size,
+                   double* out /* K x p x MMB_MCSE_FIELDS */);
+int mmb_change_counts(mmb_engine* e, int64_t* out /* p + 1 */);
+
 /* Timing / sync (bench.py roofline) */
 int mmb_sync(mmb_engine* e);
 /* Device time of the last mmb_run window's kernel launches (time_kernels nonzero).  A sweep window

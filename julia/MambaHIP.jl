@@ -88,6 +88,28 @@ gr_len(e) = ccall((:mmb_gr_len, libmambahip), Int64, (Ptr{Void},), e)
 num_kept(e) = ccall((:mmb_num_kept, libmambahip), Int64, (Ptr{Void},), e)
 reserve_draws(e, nkept::Integer) =
     check(ccall((:mmb_reserve_draws, libmambahip), Cint, (Ptr{Void}, Int64), e, nkept), e)
+# upload draws (n x p x chains, the Chains value layout) as the device-kept window, and the
+# per-chain diagnostics of that window (autocor / changerate / gewekediag / mcse partials);
+# windows are 0-based half-open [i0, i1), outputs C row-major, i.e. reversed dims in Julia
+const MMB_DIAG_MAX_LAGS = 16
+const MMB_MCSE_FIELDS = 4
+const MMB_MCSE_BM, MMB_MCSE_IMSE, MMB_MCSE_IPSE = 0, 1, 2
+set_draws!(e, value::Array{Float64,3}) =
+  check(ccall((:mmb_set_draws, libmambahip), Cint, (Ptr{Void}, Ptr{Float64}, Int64), e, value, size(value, 1)), e)
+function chain_autocov(e, i0::Integer, i1::Integer, lags::Vector{Int64})
+  out = zeros(Float64, 2 + length(lags), Int(num_monitored(e)), Int(num_chains(e)))
+  check(ccall((:mmb_chain_autocov, libmambahip), Cint, (Ptr{Void}, Int64, Int64, Cint, Ptr{Int64}, Ptr{Float64}),
+              e, i0, i1, length(lags), lags, out), e); out
+end
+function chain_mcse(e, i0::Integer, i1::Integer, etype::Integer, batch_size::Integer=100)
+  out = zeros(Float64, MMB_MCSE_FIELDS, Int(num_monitored(e)), Int(num_chains(e)))
+  check(ccall((:mmb_chain_mcse, libmambahip), Cint, (Ptr{Void}, Int64, Int64, Cint, Int64, Ptr{Float64}),
+              e, i0, i1, etype, batch_size, out), e); out
+end
+function change_counts(e)
+  out = zeros(Int64, Int(num_monitored(e)) + 1)
+  check(ccall((:mmb_change_counts, libmambahip), Cint, (Ptr{Void}, Ptr{Int64}), e, out), e); out
+end
 
 # the one collective (mmb_comm_*): RCCL over xGMI inside the library
 function comm_id()

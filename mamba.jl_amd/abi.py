@@ -17,6 +17,8 @@ MMB_SAMPLER_HMC, MMB_SAMPLER_MALA = 6, 7
 MMB_ABI_VERSION = 10
 MMB_GRAD_DEFAULT, MMB_GRAD_FORWARD, MMB_GRAD_ANALYTIC = 0, 1, 2
 MMB_SUMMARY_FIELDS, MMB_ORDER_MAX_TARGETS = 10, 16
+MMB_DIAG_MAX_LAGS, MMB_MCSE_FIELDS = 16, 4
+MMB_MCSE_BM, MMB_MCSE_IMSE, MMB_MCSE_IPSE = 0, 1, 2
 MMB_ADAPT_ALL, MMB_ADAPT_BURNIN, MMB_ADAPT_NONE = 0, 1, 2
 MMB_SLICE_MULTIVARIATE, MMB_SLICE_UNIVARIATE = 0, 1
 MMB_LINE_BETA, MMB_LINE_S2 = 0, 1
@@ -108,6 +110,10 @@ def _declare(lib):
         "mmb_num_kept": (I64, [P]),
         "mmb_get_draws": (C.c_int, [P, D]),
         "mmb_reserve_draws": (C.c_int, [P, I64]),
+        "mmb_set_draws": (C.c_int, [P, D, I64]),
+        "mmb_chain_autocov": (C.c_int, [P, I64, I64, C.c_int, C.POINTER(I64), D]),
+        "mmb_chain_mcse": (C.c_int, [P, I64, I64, C.c_int, I64, D]),
+        "mmb_change_counts": (C.c_int, [P, C.POINTER(I64)]),
         "mmb_gr_range": (C.c_int, [P, D]),
         "mmb_gr_len": (I64, [P]),
         "mmb_gr_partials": (C.c_int, [P, C.POINTER(I32), D, D]),

@@ -39,6 +39,12 @@ hipError_t mmb_launch_order_hist(int P, int j, int64_t n, int K, const double* d
                                  const uint64_t* prefix, int pass, unsigned long long* counts, hipStream_t st);
 hipError_t mmb_launch_gr_stats(int pmon, int64_t n, int K, const double* draws, const int32_t* link,
                                const double* shift, double* stats, hipStream_t st);
+hipError_t mmb_launch_chain_autocov(int P, int K, int64_t i0, int64_t i1, int nlags, const int64_t* lags,
+                                    const double* draws, double* out, hipStream_t st);
+hipError_t mmb_launch_chain_mcse(int P, int K, int64_t i0, int64_t i1, int etype, int64_t bs, const double* draws,
+                                 double* out, hipStream_t st);
+hipError_t mmb_launch_change_counts(int P, int K, int64_t n, const double* draws, unsigned long long* out,
+                                    hipStream_t st);
 
 hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
 
@@ -1812,6 +1818,25 @@ int mmb_get_draws(mmb_engine* e, double* draws) {
   return 0;
 }
 
+int mmb_set_draws(mmb_engine* e, const double* draws, int64_t nkept) {
+  if (!e || !draws) return fail(e, MMB_E_ARG, "null argument");
+  if (nkept < 1) return fail(e, MMB_E_ARG, "nkept must be >= 1");
+  const int rc = mmb_reserve_draws(e, nkept);   // mmb_init_chains called; grows the buffer
+  if (rc != 0) return rc;
+  // Chains value (n x p x m column-major) -> device layout draws[(i*p + j)*K + k]
+  std::vector<double> h((size_t)nkept * e->pmon * e->K);
+  for (int64_t k = 0; k < e->K; ++k)
+    for (int j = 0; j < e->pmon; ++j)
+      for (int64_t i = 0; i < nkept; ++i)
+        h[(i * e->pmon + j) * e->K + k] = draws[i + nkept * (j + (int64_t)e->pmon * k)];
+  HIPCHK(e, hipSetDevice(e->device));
+  e->n_kept = 0;
+  HIPCHK(e, hipMemcpyAsync(e->d_draws, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->n_kept = nkept;
+  return 0;
+}
+
 // ---------------------------------------------------------------- tune (canonical layout)
 
 // The 32-lane factorization (samplers.h pchol32: rats, node IR) keeps the AMM factor in
@@ -2095,6 +2120,79 @@ int mmb_order_hist(mmb_engine* e, int param, int ntargets, const uint64_t* prefi
   (void)hipFree(dp);
   (void)hipFree(dc);
   if (st != hipSuccess) return fail(e, MMB_E_HIP, "order_hist: %s", hipGetErrorString(st));
+  return 0;
+}
+
+// ---------------------------------------------------------------- per-chain diagnostics
+static int diag_window(mmb_engine* e, int64_t i0, int64_t i1) {
+  if (i0 < 0 || i1 <= i0 || i1 > e->n_kept)
+    return fail(e, MMB_E_ARG, "window [%lld, %lld) is not inside the %lld kept draws", (long long)i0, (long long)i1,
+                (long long)e->n_kept);
+  return 0;
+}
+
+// launch (on the engine's stream) into a device buffer of `nout` doubles, copy back, free
+template <class Launch>
+static int diag_run(mmb_engine* e, const char* what, size_t nout, double* out, Launch launch) {
+  HIPCHK(e, hipSetDevice(e->device));
+  double* dout = nullptr;
+  HIPCHK(e, hipMalloc(&dout, nout * sizeof(double)));
+  hipError_t st = launch(dout);
+  if (st == hipSuccess) st = hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+  (void)hipFree(dout);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "%s: %s", what, hipGetErrorString(st));
+  return 0;
+}
+
+int mmb_chain_autocov(mmb_engine* e, int64_t i0, int64_t i1, int nlags, const int64_t* lags, double* out) {
+  if (!e || !out || (nlags > 0 && !lags)) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  if (int rc = diag_window(e, i0, i1)) return rc;
+  if (nlags < 0 || nlags > MMB_DIAG_MAX_LAGS) return fail(e, MMB_E_ARG, "0 <= nlags <= %d", MMB_DIAG_MAX_LAGS);
+  for (int q = 0; q < nlags; ++q)
+    if (lags[q] < 1 || lags[q] >= i1 - i0)
+      return fail(e, MMB_E_ARG, "lags must be less than the sample length (lag %lld, window of %lld)",
+                  (long long)lags[q], (long long)(i1 - i0));
+  const int p = e->pmon;
+  return diag_run(e, "chain_autocov", (size_t)e->K * p * (2 + nlags), out, [&](double* dout) {
+    return mmb_launch_chain_autocov(p, (int)e->K, i0, i1, nlags, lags, e->d_draws, dout, e->stream);
+  });
+}
+
+int mmb_chain_mcse(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size, double* out) {
+  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  if (int rc = diag_window(e, i0, i1)) return rc;
+  const int64_t nw = i1 - i0;
+  if (etype == MMB_MCSE_BM) {
+    if (batch_size < 1) return fail(e, MMB_E_ARG, "batch size must be positive");
+    if (nw / batch_size < 2)   // mcse.jl:13-16
+      return fail(e, MMB_E_ARG, "iterations are < %lld and batch size is > %lld", (long long)(2 * batch_size),
+                  (long long)(nw / 2));
+  } else if (etype == MMB_MCSE_IMSE || etype == MMB_MCSE_IPSE) {
+    if (nw < 2) return fail(e, MMB_E_ARG, "lags must be less than the sample length (lag 1, window of 1)");
+  } else {
+    return fail(e, MMB_E_ARG, "unsupported mcse method %d", etype);
+  }
+  const int p = e->pmon;
+  return diag_run(e, "chain_mcse", (size_t)e->K * p * MMB_MCSE_FIELDS, out, [&](double* dout) {
+    return mmb_launch_chain_mcse(p, (int)e->K, i0, i1, etype, batch_size, e->d_draws, dout, e->stream);
+  });
+}
+
+int mmb_change_counts(mmb_engine* e, int64_t* out) {
+  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  HIPCHK(e, hipSetDevice(e->device));
+  const size_t nb = (size_t)(e->pmon + 1) * sizeof(unsigned long long);
+  unsigned long long* dc = nullptr;
+  HIPCHK(e, hipMalloc(&dc, nb));
+  hipError_t st = mmb_launch_change_counts(e->pmon, (int)e->K, e->n_kept, e->d_draws, dc, e->stream);
+  if (st == hipSuccess) st = hipMemcpyAsync(out, dc, nb, hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+  (void)hipFree(dc);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "change_counts: %s", hipGetErrorString(st));
   return 0;
 }
 

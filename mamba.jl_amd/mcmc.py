@@ -216,6 +216,41 @@ class Engine:
                                           out.ctypes.data_as(u64)))
         return out
 
+    def set_draws(self, value):
+        """Upload `value` (n x p x chains, the Chains layout) as the device-kept draws
+        (mmb_set_draws, the inverse of `draws`): the device summaries then run on it."""
+        v = np.asarray(value, dtype=np.float64)
+        if v.ndim != 3 or v.shape[1] != self.pmon or v.shape[2] != self.K or v.shape[0] < 1:
+            raise ArgumentError(f"draws must be n x {self.pmon} x {self.K} with n >= 1, got {v.shape}")
+        v = np.asfortranarray(v)
+        self._chk(self.lib.mmb_set_draws(self.h, abi.dptr(v), v.shape[0]))
+
+    # per-chain diagnostics of the device-kept draws (diag.py applies the closing formulas)
+    def chain_autocov(self, i0, i1, lags):
+        """K x p x (2 + nlags): [mean, gamma(0), gamma(lags[0]), ...] of the kept draws [i0, i1)."""
+        lg = np.ascontiguousarray(lags, dtype=np.int64).reshape(-1)
+        out = np.empty((self.K, self.pmon, 2 + lg.size))
+        self._chk(self.lib.mmb_chain_autocov(self.h, int(i0), int(i1), int(lg.size),
+                                             lg.ctypes.data_as(C.POINTER(C.c_int64)), abi.dptr(out)))
+        return out
+
+    def chain_mcse(self, i0, i1, etype, batch_size=100):
+        """K x p x [mean, gamma(0), mcse, terms] of the kept draws [i0, i1); etype "bm", "imse"
+        or "ipse" (or its MMB_MCSE_* code).  NaN where the reference's sqrt would throw."""
+        if not isinstance(etype, (int, np.integer)):
+            from .diag import etype_code
+            etype = etype_code(etype)
+        out = np.empty((self.K, self.pmon, abi.MMB_MCSE_FIELDS))
+        self._chk(self.lib.mmb_chain_mcse(self.h, int(i0), int(i1), int(etype), int(batch_size), abi.dptr(out)))
+        return out
+
+    def change_counts(self):
+        """p + 1 exact counts over this engine's chains of (chain, i >= 1) with x[i] != x[i-1]:
+        per param, then with any param changed."""
+        out = np.zeros(self.pmon + 1, dtype=np.int64)
+        self._chk(self.lib.mmb_change_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
 
 class Chains:
     """Chains / ModelChains (src/output/chains.jl:5-11, modelchains.jl): value is
@@ -262,6 +297,44 @@ class Chains:
         return {nm: {**{lb: float(ss[j, i]) for i, lb in enumerate(labels)},
                      **{f"{100 * x}%": float(qs[j, t]) for t, x in enumerate(q)}}
                 for j, nm in enumerate(self.names)}
+
+    def upload(self):
+        """Put `value` on the engine as its device-kept draws (Engine.set_draws), so the device
+        summaries and diagnostics run on chains that were read back from a file.  Explicit:
+        `read` itself uploads nothing."""
+        eng = self.engine
+        if eng is None or eng.h is None or eng.K == 0:
+            raise ArgumentError("upload needs an engine with initialised chains (read(name, model=...))")
+        eng.set_draws(self.value)
+        return self
+
+    def autocor(self, lags=(1, 5, 10, 50), relative=True):
+        """autocor(c; lags, relative) (stats.jl:3-13) per chain: (p x nlags x chains, labels).
+        As in the reference, `relative` multiplies the lags by `thin` and otherwise a lag that
+        is not a multiple of `thin` is an ArgumentError; the resulting lags are then used as
+        INDEX lags of the kept series.  With thin > 1 "Lag L" is therefore the correlation of
+        kept draws L rows apart, i.e. L * thin sampler iterations apart."""
+        from .diag import autocor
+        return autocor(self._device_engine(), lags, self.thin, relative)
+
+    def changerate(self):
+        """changerate(c) (stats.jl:19-39): the p + 1 rates [names..., Multivariate], 3 decimals."""
+        from .diag import changerate_sharded
+        return changerate_sharded(self._device_engine())
+
+    def gewekediag(self, first=0.1, last=0.5, etype="imse", batch_size=100):
+        """gewekediag(c; first, last, etype) (gewekediag.jl:3-31): p x 2 x chains,
+        [round(z, 3), round(1 - erf(|z|/sqrt(2)), 4)].  One departure from the reference: where
+        an IMSE / IPSE `value` is negative the reference's sqrt throws a DomainError; here that
+        (chain, param) gets NaN."""
+        from .diag import gewekediag
+        return gewekediag(self._device_engine(), first, last, etype, batch_size)
+
+    def mcse(self, etype="imse", batch_size=100):
+        """mcse(x, etype) (mcse.jl:3-46) of each chain's kept series: p x chains.  NaN where the
+        reference's sqrt of a negative IMSE / IPSE `value` would throw a DomainError."""
+        from .diag import mcse
+        return mcse(self._device_engine(), etype, batch_size)
 
 
 def mcmc(model, inputs, inits, iters, burnin=0, thin=1, chains=1, verbose=False, device=0,

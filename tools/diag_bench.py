@@ -1,0 +1,78 @@
+"""Timing of the per-chain diagnostics at the bench size (rats, 16384 chains, 2000 kept draws).
+
+  python tools/diag_bench.py [--iters 2000]
+
+Prints one JSON line: the bytes of one pass over the draws and the wall time (each ending in a
+sync) of autocor, changerate, gewekediag("imse") and, in the same process as the yardstick,
+summarystats; and for the IMSE windows of gewekediag the lag pairs the rule added against the
+sweeps the block scheme took (DG_PAIRS = 8 pairs per sweep; a wavefront sweeps until its last
+lane's rule has fired).  Run under `rocprofv3 --kernel-trace --stats` for per-kernel durations.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--iters", type=int, default=2000)
+ap.add_argument("--chains", type=int, default=16384)
+ap.add_argument("--reps", type=int, default=5)
+a = ap.parse_args()
+
+import numpy as np  # noqa: E402
+import torch  # noqa: F401,E402
+import _mamba_path  # noqa: E402
+
+mb = _mamba_path.load()
+DG_PAIRS = 8
+m = mb.rats()
+m.setinputs(mb.model.RATS_DATA)
+m.setsamplers(mb.model.rats_scheme_gibbs_amm())
+eng = mb.Engine(m)
+eng.init_chains(mb.model.rats_init_ls(a.chains, seed=1), seed=2)
+eng.run(a.iters, burnin=0, thin=1, draws=False, keep_device=True)
+eng.sync()
+n = eng.num_kept()
+nbytes = n * eng.pmon * a.chains * 8
+
+
+def timed(f):
+    out = f()                                  # warm
+    eng.sync()
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        out = f()
+        eng.sync()
+    return (time.perf_counter() - t0) / a.reps, out
+
+
+t_ac, (ac, _) = timed(lambda: mb.autocor(eng))
+t_cr, cr = timed(lambda: mb.changerate_sharded(eng))
+t_gw, gw = timed(lambda: mb.gewekediag(eng, etype="imse"))
+t_ss, ss = timed(lambda: mb.summarystats_sharded(eng))
+
+# IMSE block scheme on the two Geweke windows: pairs examined per lane = init + added + the one
+# that broke; a wavefront (64 adjacent chains of one param) takes its slowest lane's sweeps
+imse = {}
+for name, (i0, i1) in zip(("first", "last"), mb.geweke_windows(n)):
+    terms = eng.chain_mcse(i0, i1, "imse")[:, :, mb.diag.F_TERMS]          # K x p
+    mpairs = (i1 - i0 - 2) // 2
+    examined = np.minimum(terms + 2, mpairs + 1)
+    sweeps = np.ceil(examined / DG_PAIRS)
+    pad = (-sweeps.shape[0]) % 64
+    wave = np.pad(sweeps, ((0, pad), (0, 0))).reshape(-1, 64, sweeps.shape[1]).max(1)
+    imse[name] = {"window": [i0, i1], "window_bytes": (i1 - i0) * eng.pmon * a.chains * 8,
+                  "pairs_added_mean": float(terms.mean()), "pairs_added_max": int(terms.max()),
+                  "sweeps_lane_mean": float(sweeps.mean()), "sweeps_wave_mean": float(wave.mean()),
+                  "sweeps_wave_max": int(wave.max())}
+
+print(json.dumps({"draws_bytes": nbytes, "kept": n, "chains": a.chains,
+                  "autocor_s": t_ac, "changerate_s": t_cr, "gewekediag_imse_s": t_gw, "summarystats_s": t_ss,
+                  "imse_blocks": imse, "changerate": cr.tolist(),
+                  "autocor_mean": np.nanmean(ac, axis=2).tolist(),
+                  "geweke_abs_z_gt_2": float(np.nanmean(np.abs(gw[:, 0, :]) > 2.0)),
+                  "summarystats": ss.tolist()}))
