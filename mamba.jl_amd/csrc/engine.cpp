@@ -885,8 +885,8 @@ void mmb_destroy(mmb_engine* e) {
         hipMemcpyDtoH(h, p, sizeof h) == hipSuccess) {
       const char* names[] = {"-", "amm:load m/fl/Mv", "amm:proposal", "amm:logf x2+accept", "amm:moments+Sigma",
                              "amm:pchol", "amm:store", "gibbs", "iteration", "count", "pchol:steps",
-                             "pchol:carry", "pchol:writeback", "amwg", "slice"};
-      for (int i = 1; i < 15; ++i) fprintf(stderr, "MMB_PROF %-22s %llu\n", names[i], h[i]);
+                             "pchol:carry", "pchol:writeback", "amwg", "slice", "draws"};
+      for (int i = 1; i < 16; ++i) fprintf(stderr, "MMB_PROF %-22s %llu\n", names[i], h[i]);
     }
   }
 #ifdef MMB_PHASE_PROF
@@ -1093,7 +1093,7 @@ static int upload_blocks(mmb_engine* e) {
     d.gibbs_a = __builtin_nan("");
     if (e->model == MMB_MODEL_IR && h.spec.sampler == MMB_SAMPLER_GIBBS) {
       // a constant Gamma shape (the expression is one CONST word): the sweep kernel draws the
-      // variate with every block's draws of the iteration at once (samplers.h predraw)
+      // variate with every block's draws of a batch of iterations at once (samplers.h predraw)
       const mmb_ir_block& IB = e->ir_blocks[b];
       const int pc = IB.gibbs_expr[0];
       if (IB.gibbs_family != MMB_IR_NORMAL && pc >= 0 && pc + 1 < (int)e->ir_code.size() &&

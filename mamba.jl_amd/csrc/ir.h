@@ -447,8 +447,9 @@ struct Mdl<MMB_MODEL_IR> {
   // Gibbs closure blocks (mmb_ir_block.gibbs_*, ABI 10; a user Sampler(params, f), sampler.jl:20-24,
   // whose closure returns rand(Normal | InverseGamma | Gamma) of one scalar node, traced by the host
   // like the node functions).  The variate does not depend on the state when it is a standard normal
-  // or a Gamma of constant shape (engine.cpp: B.gibbs_a): the sweep kernel draws it with the
-  // iteration's other variates (samplers.h predraw, the same streams and values); a state-dependent
+  // or a Gamma of constant shape (engine.cpp: B.gibbs_a): the sweep kernel draws it with the other
+  // variates of max(1, 32 / nb) iterations in one pass, the interpreter and the specialised kernel
+  // alike (samplers.h predraw, the same streams and values as a draw here); a state-dependent
   // shape draws its Gamma here (mmb_gamma_any, MMB_SUB_GAMMA_N / _U).
   __device__ __forceinline__ static int gibbs_draw_kind(const DBlock& B, double* a) {
     *a = 0.0;

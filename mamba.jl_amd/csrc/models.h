@@ -446,8 +446,9 @@ struct Mdl<MMB_MODEL_RATS> {
   // The random draw of a conjugate block does not depend on the chain state: a Gamma(a)
   // variate for the s2 blocks (rand(InverseGamma(a, b)) = b / G, shape a fixed by the
   // model), a standard normal for the mu blocks.  The sweep kernel draws them for all
-  // blocks of an iteration at once, one block per lane (predraw), and passes each block
-  // its value.  Returns 1 (gamma, shape *a) or 2 (normal).
+  // blocks of several consecutive iterations at once, one (iteration, block) per lane
+  // (samplers.h predraw: 7 blocks, 4 iterations per pass), and passes each block its value.
+  // Returns 1 (gamma, shape *a) or 2 (normal).
   __device__ __forceinline__ static int gibbs_draw_kind(const DBlock& B, double* a) {
     const int n = B.nodes[0];
     if (n == MMB_RATS_MU_ALPHA || n == MMB_RATS_MU_BETA) { *a = 0.0; return 2; }

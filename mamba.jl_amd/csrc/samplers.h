@@ -14,15 +14,24 @@ struct Smp {
   using St = typename M::St;
   using Lc = typename M::Lc;
 
-  // ---------------------------------------------------------------- per-iteration draws
-  // Variates that do not depend on the chain state, drawn for every block of an iteration
-  // at once with one block per lane (32-lane groups): lane b holds block b's Gibbs variate
-  // (Mdl::gibbs_draw_kind: Gamma(a) by Marsaglia-Tsang or a standard normal) or its AMM
-  // accept uniform.  Same substreams, counters and operations as the per-block draws
+  // ---------------------------------------------------------------- batched draws
+  // Variates that do not depend on the chain state -- per block of an iteration its Gibbs
+  // variate (Mdl::gibbs_draw_kind: Gamma(a) by Marsaglia-Tsang or a standard normal) or its
+  // AMM accept uniform -- drawn for Q = max(1, 32 / nb) consecutive iterations in one pass
+  // (32-lane groups): lane l holds block l % nb of iteration it + l / nb, lanes from Q * nb on
+  // draw nothing that is used.  They depend only on (seed, chain, iteration, block, substream)
+  // and the block descriptors, so the pass fills the lanes one iteration leaves idle with the
+  // following iterations' draws and the sweep runs it on every Q-th iteration (sweep.h).  Same
+  // substreams, counters and operations as the per-block draws of each iteration
   // (mmb_gamma_mt is replayed in full whenever its first attempt does not accept), so the
   // values are bit-identical to drawing them inside the blocks.
   __device__ __forceinline__ static double predraw(const SweepArgs& A, uint32_t chain, int64_t it,
                                                    const Grp<G>& g) {
+    // q = lane / nb capped at Q - 1, by uniform steps over the batch's iterations (no per-lane
+    // division); a lane past the batch then has bl >= nb, matches no block and keeps kind 0
+    int q = 0;
+    for (int t = A.nb; A.nb > 0 && t + A.nb <= 32; t += A.nb) q += g.lane >= t ? 1 : 0;
+    const int bl = g.lane - q * A.nb;
     int kind = 0;  // 0 none, 1 Gamma(a), 2 normal, 3 uniform
     double a = 0.0;
     for (int b = 0; b < A.nb; ++b) {
@@ -31,12 +40,13 @@ struct Smp {
       int k = 0;
       if (B.kind == MMB_SAMPLER_GIBBS) k = M::gibbs_draw_kind(B, &ab);
       else if (B.kind == MMB_SAMPLER_AMM) k = 3;
-      kind = g.lane == b ? k : kind;
-      a = g.lane == b ? ab : a;
+      kind = bl == b ? k : kind;
+      a = bl == b ? ab : a;
     }
-    const uint32_t b = (uint32_t)g.lane;
-    const mmb_rng rn = mmb_rng_make(A.seed, chain, (uint32_t)it, b, kind == 1 ? MMB_SUB_GAMMA_N : MMB_SUB_NORMAL);
-    const mmb_rng ru = mmb_rng_make(A.seed, chain, (uint32_t)it, b, kind == 1 ? MMB_SUB_GAMMA_U : MMB_SUB_UNIFORM);
+    const uint32_t b = (uint32_t)bl;
+    const uint32_t itq = (uint32_t)(it + (int64_t)q);  // the iteration's own Philox key (64-bit sum, then cut)
+    const mmb_rng rn = mmb_rng_make(A.seed, chain, itq, b, kind == 1 ? MMB_SUB_GAMMA_N : MMB_SUB_NORMAL);
+    const mmb_rng ru = mmb_rng_make(A.seed, chain, itq, b, kind == 1 ? MMB_SUB_GAMMA_U : MMB_SUB_UNIFORM);
     const double x = mmb_normal(&rn, 0u);
     const double u = mmb_uniform(&ru, 0u);
     if (kind != 1) return kind == 2 ? x : u;

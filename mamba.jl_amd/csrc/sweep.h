@@ -80,15 +80,29 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
   if ((threadIdx.x & 63) == 0)
     for (int i = 0; i < 16; ++i) mmb_prof_lds()[i] = 0;
 #endif
+  // state-independent draws (32-lane groups): one pass draws them for the next Q = max(1, 32 / nb)
+  // iterations, block b of the batch's iteration j in lane j * nb + b (samplers.h predraw).  A
+  // batch starts at the launch's step 0 and on every Q-th step after it, so no draw crosses a
+  // launch; what a batch draws past the launch's last iteration is dropped.  pre0 = (step % Q) * nb,
+  // kept by addition: it wraps when another iteration's nb lanes would not fit the 32.
+  constexpr bool PREDRAW = G == 32 && (KINDS & ((1u << MMB_SAMPLER_GIBBS) | (1u << MMB_SAMPLER_AMM))) != 0u;
+  int pre0 = 0;
+  double pre = 0.0;
   for (int step = 0; step < A.n_iters; ++step) {
     const int64_t it = A.iter0 + 1 + step;
 #ifdef MMB_PHASE_PROF
     const uint64_t _it0 = __builtin_amdgcn_s_memtime();
 #endif
-    // state-independent draws of the whole iteration, one block per lane (32-lane groups)
-    double pre = 0.0;
-    if constexpr (G == 32 && (KINDS & ((1u << MMB_SAMPLER_GIBBS) | (1u << MMB_SAMPLER_AMM))) != 0u)
-      pre = S::predraw(A, chain, it, g);
+    if constexpr (PREDRAW) {
+      // (one step in Q; marked so for the block placement: the pass sits out of the iteration's
+      // straight line, which also keeps sweep_kernel<rats, Gibbs+AMM> at its 198 spilled VGPRs
+      // against 207 unmarked)
+      if (__builtin_expect(pre0 == 0, 0)) {
+        MMB_PROF_START
+        pre = S::predraw(A, chain, it, g);
+        MMB_PROF_MARK(15, g.lane)
+      }
+    }
     for (int b = 0; b < A.nb; ++b) {
       // descriptor read through the constant address space: uniform scalar loads (s_load,
       // scalar cache) instead of vector loads that wait on the vector memory path
@@ -107,7 +121,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
           break;
         case MMB_SAMPLER_AMM:
           if constexpr ((KINDS >> MMB_SAMPLER_AMM) & 1u) S::amm(A, B, c, chain, it, b, rn, ru, adapt, s, l, g, lds,
-                                                                        G == 32 ? S::lane_value(pre, b) : 0.0);
+                                                                        G == 32 ? S::lane_value(pre, pre0 + b) : 0.0);
           break;
         case MMB_SAMPLER_SLICE:
           if constexpr ((KINDS >> MMB_SAMPLER_SLICE) & 1u) {
@@ -130,7 +144,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
           const mmb_rng gu = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_U);
           MMB_PROF_START
-          M::gibbs(A, B, s, l, g, &rn, &gn, &gu, G == 32 ? S::lane_value(pre, b) : 0.0);
+          M::gibbs(A, B, s, l, g, &rn, &gn, &gu, G == 32 ? S::lane_value(pre, pre0 + b) : 0.0);
           MMB_PROF_MARK(7, g.lane)
         }
           break;
@@ -144,6 +158,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
       mmb_prof_lds()[9] += 1;
     }
 #endif
+    pre0 += A.nb;
+    if (pre0 + A.nb > 32) pre0 = 0;
     if (A.draws && it > A.burnin && (it - A.burnin) % A.thin == 0) {
       const int64_t row = (it - A.burnin) / A.thin - 1 - A.kept_origin;
       M::write_draws(A, s, g, row, c);
