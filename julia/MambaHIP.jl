@@ -110,6 +110,26 @@ function change_counts(e)
   out = zeros(Int64, Int(num_monitored(e)) + 1)
   check(ccall((:mmb_change_counts, libmambahip), Cint, (Ptr{Void}, Ptr{Int64}), e, out), e); out
 end
+# heideldiag / rafterydiag partials: [mean, W] of the suffix windows from 0-based starts, mcse
+# with a window start per (param, chain) (i0 is p x chains here: reversed dims), and the
+# Raftery-Lewis state [threshold, kthin, ntest, n00, n10, n01, n11, bic]
+const MMB_HEIDEL_MAX_STARTS = 16
+const MMB_RAFTERY_FIELDS = 8
+function chain_cvm(e, starts::Vector{Int64})
+  out = zeros(Float64, 2, length(starts), Int(num_monitored(e)), Int(num_chains(e)))
+  check(ccall((:mmb_chain_cvm, libmambahip), Cint, (Ptr{Void}, Cint, Ptr{Int64}, Ptr{Float64}),
+              e, length(starts), starts, out), e); out
+end
+function chain_mcse_from(e, i0::Matrix{Int64}, i1::Integer, etype::Integer, batch_size::Integer=100)
+  size(i0) == (Int(num_monitored(e)), Int(num_chains(e))) || throw(ArgumentError("i0 must be p x chains"))
+  out = zeros(Float64, MMB_MCSE_FIELDS, Int(num_monitored(e)), Int(num_chains(e)))
+  check(ccall((:mmb_chain_mcse_from, libmambahip), Cint, (Ptr{Void}, Ptr{Int64}, Int64, Cint, Int64, Ptr{Float64}),
+              e, i0, i1, etype, batch_size, out), e); out
+end
+function chain_raftery(e, q::Real)
+  out = zeros(Float64, MMB_RAFTERY_FIELDS, Int(num_monitored(e)), Int(num_chains(e)))
+  check(ccall((:mmb_chain_raftery, libmambahip), Cint, (Ptr{Void}, Cdouble, Ptr{Float64}), e, q, out), e); out
+end
 
 # the one collective (mmb_comm_*): RCCL over xGMI inside the library
 function comm_id()

@@ -19,6 +19,7 @@ MMB_GRAD_DEFAULT, MMB_GRAD_FORWARD, MMB_GRAD_ANALYTIC = 0, 1, 2
 MMB_SUMMARY_FIELDS, MMB_ORDER_MAX_TARGETS = 10, 16
 MMB_DIAG_MAX_LAGS, MMB_MCSE_FIELDS = 16, 4
 MMB_MCSE_BM, MMB_MCSE_IMSE, MMB_MCSE_IPSE = 0, 1, 2
+MMB_HEIDEL_MAX_STARTS, MMB_RAFTERY_FIELDS = 16, 8
 MMB_ADAPT_ALL, MMB_ADAPT_BURNIN, MMB_ADAPT_NONE = 0, 1, 2
 MMB_SLICE_MULTIVARIATE, MMB_SLICE_UNIVARIATE = 0, 1
 MMB_LINE_BETA, MMB_LINE_S2 = 0, 1
@@ -114,6 +115,9 @@ def _declare(lib):
         "mmb_chain_autocov": (C.c_int, [P, I64, I64, C.c_int, C.POINTER(I64), D]),
         "mmb_chain_mcse": (C.c_int, [P, I64, I64, C.c_int, I64, D]),
         "mmb_change_counts": (C.c_int, [P, C.POINTER(I64)]),
+        "mmb_chain_cvm": (C.c_int, [P, C.c_int, C.POINTER(I64), D]),
+        "mmb_chain_mcse_from": (C.c_int, [P, C.POINTER(I64), I64, C.c_int, I64, D]),
+        "mmb_chain_raftery": (C.c_int, [P, C.c_double, D]),
         "mmb_gr_range": (C.c_int, [P, D]),
         "mmb_gr_len": (I64, [P]),
         "mmb_gr_partials": (C.c_int, [P, C.POINTER(I32), D, D]),

@@ -45,6 +45,12 @@ hipError_t mmb_launch_chain_mcse(int P, int K, int64_t i0, int64_t i1, int etype
                                  double* out, hipStream_t st);
 hipError_t mmb_launch_change_counts(int P, int K, int64_t n, const double* draws, unsigned long long* out,
                                     hipStream_t st);
+hipError_t mmb_launch_chain_cvm(int P, int K, int64_t n, int nstarts, const int64_t* starts, const double* draws,
+                                double* out, hipStream_t st);
+hipError_t mmb_launch_chain_mcse_from(int P, int K, const int64_t* i0s, int64_t i1, int etype, int64_t bs,
+                                      const double* draws, double* out, hipStream_t st);
+hipError_t mmb_launch_chain_raftery(int P, int K, int64_t n, int64_t rlo, int interp, double h, const double* draws,
+                                    double* out, hipStream_t st);
 
 hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
 
@@ -2160,9 +2166,8 @@ int mmb_chain_autocov(mmb_engine* e, int64_t i0, int64_t i1, int nlags, const in
   });
 }
 
-int mmb_chain_mcse(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size, double* out) {
-  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+// the window and method checks of mmb_chain_mcse
+static int mcse_window(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size) {
   if (int rc = diag_window(e, i0, i1)) return rc;
   const int64_t nw = i1 - i0;
   if (etype == MMB_MCSE_BM) {
@@ -2175,9 +2180,79 @@ int mmb_chain_mcse(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t bat
   } else {
     return fail(e, MMB_E_ARG, "unsupported mcse method %d", etype);
   }
+  return 0;
+}
+
+int mmb_chain_mcse(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size, double* out) {
+  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  if (int rc = mcse_window(e, i0, i1, etype, batch_size)) return rc;
   const int p = e->pmon;
   return diag_run(e, "chain_mcse", (size_t)e->K * p * MMB_MCSE_FIELDS, out, [&](double* dout) {
     return mmb_launch_chain_mcse(p, (int)e->K, i0, i1, etype, batch_size, e->d_draws, dout, e->stream);
+  });
+}
+
+// heideldiag.jl:11-16 on every candidate window at once
+int mmb_chain_cvm(mmb_engine* e, int nstarts, const int64_t* starts, double* out) {
+  if (!e || !out || !starts) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  if (nstarts < 1 || nstarts > MMB_HEIDEL_MAX_STARTS)
+    return fail(e, MMB_E_ARG, "1 <= nstarts <= %d", MMB_HEIDEL_MAX_STARTS);
+  for (int q = 0; q < nstarts; ++q) {
+    if (starts[q] < 0 || starts[q] >= e->n_kept)
+      return fail(e, MMB_E_ARG, "start %lld is not inside the %lld kept draws", (long long)starts[q],
+                  (long long)e->n_kept);
+    if (q > 0 && starts[q] <= starts[q - 1]) return fail(e, MMB_E_ARG, "starts must be strictly increasing");
+  }
+  const int p = e->pmon;
+  return diag_run(e, "chain_cvm", (size_t)e->K * p * nstarts * 2, out, [&](double* dout) {
+    return mmb_launch_chain_cvm(p, (int)e->K, e->n_kept, nstarts, starts, e->d_draws, dout, e->stream);
+  });
+}
+
+// heideldiag.jl:24: mcse of each series' own window
+int mmb_chain_mcse_from(mmb_engine* e, const int64_t* i0, int64_t i1, int etype, int64_t batch_size, double* out) {
+  if (!e || !out || !i0) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  const int p = e->pmon;
+  const size_t nel = (size_t)e->K * p;
+  for (size_t q = 0; q < nel; ++q)
+    if (int rc = mcse_window(e, i0[q], i1, etype, batch_size)) {
+      const std::string why = e->err;
+      return fail(e, rc, "%s (chain %lld, param %d)", why.c_str(), (long long)(q / p), (int)(q % p));
+    }
+  HIPCHK(e, hipSetDevice(e->device));
+  int64_t* di = nullptr;
+  HIPCHK(e, hipMalloc(&di, nel * sizeof(int64_t)));
+  hipError_t st = hipMemcpyAsync(di, i0, nel * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
+  int rc = 0;
+  if (st != hipSuccess) rc = fail(e, MMB_E_HIP, "chain_mcse_from: %s", hipGetErrorString(st));
+  else
+    rc = diag_run(e, "chain_mcse_from", nel * MMB_MCSE_FIELDS, out, [&](double* dout) {
+      return mmb_launch_chain_mcse_from(p, (int)e->K, di, i1, etype, batch_size, e->d_draws, dout, e->stream);
+    });
+  (void)hipFree(di);
+  return rc;
+}
+
+// rafterydiag.jl:13-34; the quantile index is Julia 0.5 quantile's, split here
+int mmb_chain_raftery(mmb_engine* e, double q, double* out) {
+  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  if (!(q > 0.0 && q < 1.0)) return fail(e, MMB_E_ARG, "q is not in (0, 1)");
+  const int64_t n = e->n_kept;
+  if (n < 3 || n > 0x7fffffffll)
+    return fail(e, MMB_E_ARG, "the Raftery-Lewis counts need 3 <= kept draws < 2^31, got %lld", (long long)n);
+  const double index = 1.0 + (double)(n - 1) * q;
+  const double lo = floor(index);
+  const double h = index - lo;
+  const int interp = index != lo;
+  const int64_t rlo = (int64_t)lo - 1;
+  if (rlo < 0 || rlo + interp >= n) return fail(e, MMB_E_ARG, "quantile index %g outside 1 .. %lld", index, (long long)n);
+  const int p = e->pmon;
+  return diag_run(e, "chain_raftery", (size_t)e->K * p * MMB_RAFTERY_FIELDS, out, [&](double* dout) {
+    return mmb_launch_chain_raftery(p, (int)e->K, n, rlo, interp, h, e->d_draws, dout, e->stream);
   });
 }
 

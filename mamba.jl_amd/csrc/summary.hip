@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "order_key.h"
+
 #define SS_THREADS 256
 #define SS_FIELDS 10
 #define OS_THREADS 256
@@ -86,12 +88,6 @@ __global__ __launch_bounds__(SS_THREADS) void ss_chain_kernel(int P, int64_t n, 
   double* o = out + ((size_t)k * P + j) * SS_FIELDS;
   o[0] = s1; o[1] = q; o[2] = b1; o[3] = b2; o[4] = nfull;
   o[5] = hsum; o[6] = hcnt; o[7] = tsum; o[8] = tcnt; o[9] = 0.0;
-}
-
-// order-preserving key: negative doubles reversed, positive ones above them
-__device__ __forceinline__ uint64_t os_key(double x) {
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
 __global__ __launch_bounds__(OS_THREADS) void os_hist_kernel(int P, int j, int64_t n, int K,

@@ -7,13 +7,31 @@ often it moved) and its within-chain drift (Geweke).  The per-element work runs 
 the arguments as the reference does, picks the windows and applies the closing formulas to the
 K x p partials.
 
+heideldiag (src/output/heideldiag.jl:3-27) and rafterydiag (src/output/rafterydiag.jl:3-47)
+are per-chain too.  Their per-element work is mmb_chain_cvm / mmb_chain_mcse_from /
+mmb_chain_raftery; what stays here is the Cramer-von Mises distribution function (pcramer,
+src/utils.jl:73-81, with scipy.special), the choice of each series' window, and the closing
+formulas, all vectorised over K x p with IEEE semantics (0/0 = NaN, x/0 = Inf, as Julia's float
+division gives them).
+
 `engine` is anything engine-shaped: num_kept(), K, pmon, chain_autocov(i0, i1, lags),
-chain_mcse(i0, i1, etype, batch_size) and change_counts().
+chain_mcse(i0, i1, etype, batch_size) and change_counts(); for the last two diagnostics also
+chain_cvm(starts), chain_mcse_from(i0, i1, etype, batch_size) and chain_raftery(q).
 
 Rounding: Julia's round (round(Int, x) for the Geweke windows, round(x, digits) for the
 reported figures) rounds to nearest with ties to even, as Python's round and numpy's do.
+Julia 0.5's round(x, digits) is round(x * 10^digits) / 10^digits; np.round computes the same
+three operations (scale, rint, unscale), so the rounded p-values are the reference's for the
+same unrounded value.
+
+Departures from the reference, beyond NaN for a DomainError: heideldiag refuses fewer than 10
+draws (delta = trunc(0.10 n) is then 0 and the reference's loop never ends for a series that
+does not converge at its first window); rafterydiag reports NaN for a series whose thinned
+test sequence drops below 3 elements before bic turns negative (the reference: DomainError
+from log(-1)).
 """
 import math
+import warnings
 
 import numpy as np
 
@@ -126,3 +144,106 @@ def mcse(engine, etype="imse", batch_size=100):
     n = engine.num_kept()
     _check_mcse_window(n, code, batch_size)
     return engine.chain_mcse(0, n, code, batch_size)[:, :, F_MCSE].T
+
+
+def pcramer(q):
+    """pcramer(q) (utils.jl:73-81): the distribution function of the Cramer-von Mises statistic,
+    the first four terms of its series; elementwise over an array."""
+    from scipy import special
+    q = np.asarray(q, dtype=np.float64)
+    p = np.zeros_like(q)
+    with np.errstate(all="ignore"):
+        for k in range(4):
+            c1 = 4.0 * k + 1.0
+            c2 = c1 * c1 / (16.0 * q)
+            p = p + special.gamma(k + 0.5) / math.factorial(k) * math.sqrt(c1) * np.exp(-c2) * special.kv(0.25, c2)
+        return p / (math.pi ** 1.5 * np.sqrt(q))
+
+
+def heidel_starts(n):
+    """The candidate windows of heideldiag.jl:6-10, 22: (0-based starts s_j = j delta of the
+    1-based i = 1, 1 + delta, ... < n / 2, and the first i >= n / 2)."""
+    delta = int(0.10 * n)                       # trunc(Int, 0.10 * n)
+    starts, i = [], 1
+    while i < n / 2:
+        starts.append(i - 1)
+        i += delta
+    return starts, i
+
+
+def heideldiag(engine, alpha=0.05, eps=0.1, etype="imse", batch_size=100, start=1):
+    """heideldiag(c; alpha, eps, etype, start) (heideldiag.jl:3-27): p x 6 x K, [Burn-in,
+    Stationarity, p-value, Mean, Halfwidth, Test].  A series that never converges keeps the
+    p-value, mean and halfwidth of the last window tested and reports the first i >= n / 2."""
+    from scipy import special
+    code = etype_code(etype)
+    n = engine.num_kept()
+    if n < 10:
+        raise ArgumentError(f"heideldiag needs at least 10 iterations, got {n}")
+    h0 = int(n / 2) - 1                         # x[trunc(Int, n / 2):end], 0-based
+    _check_mcse_window(n - h0, code, batch_size)  # the shortest window any series gets
+    starts, i_final = heidel_starts(n)
+    half = engine.chain_mcse(h0, n, code, batch_size)
+    cv = engine.chain_cvm(starts)               # K x p x candidates x [mean, W]
+    with np.errstate(all="ignore"):
+        S0 = (n - h0) * half[:, :, F_MCSE] ** 2
+        pv = 1.0 - pcramer(cv[:, :, :, 1] / S0[:, :, None])
+        conv = pv > alpha                       # NaN: not converged
+        ok = conv.any(axis=2)
+        sel = np.where(ok, conv.argmax(axis=2), len(starts) - 1)
+        s_sel = np.asarray(starts, dtype=np.int64)[sel]
+        pvalue = np.take_along_axis(pv, sel[:, :, None], axis=2)[:, :, 0]
+        ybar = np.take_along_axis(cv[:, :, :, 0], sel[:, :, None], axis=2)[:, :, 0]
+        m = engine.chain_mcse_from(s_sel, n, code, batch_size)
+        halfwidth = math.sqrt(2.0) * float(special.erfinv(1.0 - alpha)) * m[:, :, F_MCSE]
+        passed = halfwidth / np.abs(ybar) <= eps
+        burnin = np.where(ok, s_sel + 1, i_final) + start - 2
+        out = np.stack([burnin.astype(np.float64), ok.astype(np.float64), np.round(pvalue, 4), ybar, halfwidth,
+                        passed.astype(np.float64)], axis=2)
+    return out.transpose(1, 2, 0)
+
+
+def raftery_nmin(q, r, s):
+    """(phi, nmin) of rafterydiag.jl:7-8."""
+    from scipy import special
+    phi = math.sqrt(2.0) * float(special.erfinv(s))
+    return phi, int(math.ceil(q * (1.0 - q) * ((phi / r) * (phi / r))))
+
+
+def raftery_from_counts(kthin, n00, n10, n01, n11, phi, nmin, r, eps, start=1, thin=1):
+    """rafterydiag.jl:35-46 on the final transition counts: [kthin, burnin, total, nmin,
+    total / nmin] along a new last axis."""
+    with np.errstate(all="ignore"):
+        alpha = n01 / (n00 + n01)
+        beta = n10 / (n10 + n11)
+        kthin = kthin * thin
+        ab = alpha + beta
+        m = np.log(eps * ab / np.maximum(alpha, beta)) / np.log(np.abs(1.0 - alpha - beta))
+        burnin = kthin * np.ceil(m) + start - 1
+        nn = ((2.0 - alpha - beta) * alpha * beta * (phi * phi)) / ((r * r) * (ab * ab * ab))
+        total = burnin + kthin * np.ceil(nn)
+        return np.stack([kthin, burnin, total, np.full_like(total, float(nmin)), total / nmin], axis=-1)
+
+
+def rafterydiag(engine, q=0.025, r=0.005, s=0.95, eps=0.001, start=1, thin=1):
+    """rafterydiag(c; q, r, s, eps) (rafterydiag.jl:3-47): p x 5 x K, [Thinning, Burn-in, Total,
+    Nmin, Dependence Factor]."""
+    if not 0.0 < q < 1.0:
+        raise ArgumentError("q is not in (0, 1)")
+    if not 0.0 < s < 1.0:
+        raise ArgumentError("s is not in (0, 1)")
+    if not r > 0.0:
+        raise ArgumentError("r must be positive")
+    if not eps > 0.0:
+        raise ArgumentError("eps must be positive")
+    n = engine.num_kept()
+    phi, nmin = raftery_nmin(q, r, s)
+    if nmin > n:
+        warnings.warn(f"At least {nmin} samples are needed for specified q, r, and s")
+        out = np.full((engine.pmon, 5, engine.K), np.nan)
+        out[:, 3, :] = nmin
+        return out
+    rf = engine.chain_raftery(q)                # K x p x [threshold, kthin, ntest, n00, n10, n01, n11, bic]
+    out = raftery_from_counts(rf[:, :, 1], rf[:, :, 3], rf[:, :, 4], rf[:, :, 5], rf[:, :, 6], phi, nmin, r, eps,
+                              start, thin)
+    return out.transpose(1, 2, 0)

@@ -94,6 +94,38 @@ def gelmandiag_sharded(engine, allreduce_sum=None, allreduce_minmax=None, transf
     return psrf_from_sums(tot, n, p, alpha=alpha, mpsrf=mpsrf)
 
 
+def cor_from_sums(sums, n, p):
+    """cor(combine(c)) (stats.jl:15-17) from the Gelman-Rubin sums taken with identity links: the
+    pooled sum of squares about the pooled mean is the within-chain part (n - 1) A3 plus the
+    between-chain part n (A2 - A1 A1' / m); rho_ij = SS_ij / sqrt(SS_ii SS_jj), diagonal 1.0.
+    A common shift of the draws leaves it unchanged."""
+    sums = np.asarray(sums, dtype=np.float64)
+    m = sums[0]
+    A1 = sums[1:1 + p]
+    A2 = sums[1 + p:1 + p + p * p].reshape(p, p)
+    A3 = sums[1 + p + p * p:1 + p + 2 * p * p].reshape(p, p)
+    SS = (n - 1) * A3 + n * (A2 - np.outer(A1, A1) / m)
+    d = np.sqrt(np.diag(SS))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = SS / np.outer(d, d)
+    rho[np.diag_indices(p)] = 1.0
+    return rho
+
+
+def cor_sharded(engine, allreduce_sum=None, allreduce_minmax=None):
+    """cor(c) over all chains of all ranks: p x p.  The sums are gelmandiag_sharded's with
+    identity links and the mid-range shift; across ranks they need the sum all-reduce alone
+    (and the range all-reduce for a common shift)."""
+    p = engine.pmon
+    mm = engine.gr_range()
+    lo, hi = mm[:, 0].copy(), mm[:, 1].copy()
+    if allreduce_minmax is not None:
+        lo, hi = allreduce_minmax(lo, hi)
+    local = engine.gr_partials(np.zeros(p, dtype=np.int32), 0.5 * (lo + hi))
+    tot = allreduce_sum(local) if allreduce_sum is not None else local
+    return cor_from_sums(tot, engine.num_kept(), p)
+
+
 def gelmandiag(chains, alpha=0.05, mpsrf=False, transform=False):
     """Host gelmandiag on an n x p x m array (reference formula, gelmandiag.jl:3-60)."""
     psi = np.asarray(chains.value if hasattr(chains, "value") else chains, dtype=np.float64)

@@ -244,6 +244,35 @@ class Engine:
         self._chk(self.lib.mmb_chain_mcse(self.h, int(i0), int(i1), int(etype), int(batch_size), abi.dptr(out)))
         return out
 
+    def chain_cvm(self, starts):
+        """K x p x nstarts x [mean, W] of the suffix windows [s, n) of the kept draws, for 0-based
+        strictly increasing `starts`: W = sum_t B_t^2 / m^2 of heideldiag.jl:14-16 (no 1 / S0)."""
+        st = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+        out = np.empty((self.K, self.pmon, st.size, 2))
+        self._chk(self.lib.mmb_chain_cvm(self.h, int(st.size), st.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         abi.dptr(out)))
+        return out
+
+    def chain_mcse_from(self, i0, i1, etype, batch_size=100):
+        """chain_mcse with a window start per (chain, param): `i0` is K x p, the end `i1` common."""
+        if not isinstance(etype, (int, np.integer)):
+            from .diag import etype_code
+            etype = etype_code(etype)
+        i0 = np.ascontiguousarray(i0, dtype=np.int64)
+        if i0.shape != (self.K, self.pmon):
+            raise ArgumentError(f"window starts must be {self.K} x {self.pmon}, got {i0.shape}")
+        out = np.empty((self.K, self.pmon, abi.MMB_MCSE_FIELDS))
+        self._chk(self.lib.mmb_chain_mcse_from(self.h, i0.ctypes.data_as(C.POINTER(C.c_int64)), int(i1), int(etype),
+                                               int(batch_size), abi.dptr(out)))
+        return out
+
+    def chain_raftery(self, q):
+        """K x p x [threshold, kthin, ntest, n00, n10, n01, n11, bic] (rafterydiag.jl:13-34) of the
+        kept draws; kthin NaN where the thinned series ran out before bic turned negative."""
+        out = np.empty((self.K, self.pmon, abi.MMB_RAFTERY_FIELDS))
+        self._chk(self.lib.mmb_chain_raftery(self.h, float(q), abi.dptr(out)))
+        return out
+
     def change_counts(self):
         """p + 1 exact counts over this engine's chains of (chain, i >= 1) with x[i] != x[i-1]:
         per param, then with any param changed."""
@@ -335,6 +364,30 @@ class Chains:
         reference's sqrt of a negative IMSE / IPSE `value` would throw a DomainError."""
         from .diag import mcse
         return mcse(self._device_engine(), etype, batch_size)
+
+    def heideldiag(self, alpha=0.05, eps=0.1, etype="imse", batch_size=100):
+        """heideldiag(c; alpha, eps, etype) (heideldiag.jl:3-41): p x 6 x chains, [Burn-in,
+        Stationarity, p-value, Mean, Halfwidth, Test], Burn-in counted from `start` as the
+        reference counts it from start(c.range).  Departures: fewer than 10 kept draws are an
+        ArgumentError (the reference's step is then 0 and it never returns for a series that
+        does not converge at once), and NaN stands where the sqrt of a negative IMSE / IPSE
+        `value` would throw a DomainError."""
+        from .diag import heideldiag
+        return heideldiag(self._device_engine(), alpha, eps, etype, batch_size, self.start)
+
+    def rafterydiag(self, q=0.025, r=0.005, s=0.95, eps=0.001):
+        """rafterydiag(c; q, r, s, eps) (rafterydiag.jl:3-61): p x 5 x chains, [Thinning, Burn-in,
+        Total, Nmin, Dependence Factor], with `start` and `thin` where the reference takes
+        start(c.range) and step(range).  Departure: a series whose thinned test sequence falls
+        below 3 elements before bic turns negative gets NaN (the reference ends in a DomainError
+        from log(-1))."""
+        from .diag import rafterydiag
+        return rafterydiag(self._device_engine(), q, r, s, eps, self.start, self.thin)
+
+    def cor(self):
+        """cor(c) (stats.jl:15-17): the p x p correlation matrix of the draws pooled over chains."""
+        from .gelman import cor_sharded
+        return cor_sharded(self._device_engine())
 
 
 def mcmc(model, inputs, inits, iters, burnin=0, thin=1, chains=1, verbose=False, device=0,

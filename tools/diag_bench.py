@@ -6,7 +6,12 @@ Prints one JSON line: the bytes of one pass over the draws and the wall time (ea
 sync) of autocor, changerate, gewekediag("imse") and, in the same process as the yardstick,
 summarystats; and for the IMSE windows of gewekediag the lag pairs the rule added against the
 sweeps the block scheme took (DG_PAIRS = 8 pairs per sweep; a wavefront sweeps until its last
-lane's rule has fired).  Run under `rocprofv3 --kernel-trace --stats` for per-kernel durations.
+lane's rule has fired).  For heideldiag("imse") and rafterydiag(q=0.1, r=0.05, s=0.9) (at the
+defaults Nmin = 3746 exceeds the 2000 kept draws and no kernel would run): the wall times, the
+passes each kernel's algorithm makes over its window, and per wavefront the sweeps of the
+Raftery-Lewis selection (fixed by the digit width) and of its thinning loop (a wavefront sweeps
+until its last lane's bic is negative; the sweep at kthin reads every kthin-th row).
+Run under `rocprofv3 --kernel-trace --stats` for per-kernel durations.
 """
 import argparse
 import json
@@ -70,8 +75,49 @@ for name, (i0, i1) in zip(("first", "last"), mb.geweke_windows(n)):
                   "sweeps_lane_mean": float(sweeps.mean()), "sweeps_wave_mean": float(wave.mean()),
                   "sweeps_wave_max": int(wave.max())}
 
+t_hd, hd = timed(lambda: mb.heideldiag(eng, etype="imse"))
+RQ, RR, RS = 0.1, 0.05, 0.9
+t_rf, rf = timed(lambda: mb.rafterydiag(eng, RQ, RR, RS))
+
+
+def per_wave(x):
+    """max over each wavefront (64 adjacent chains of one param) of a K x p array"""
+    pad = (-x.shape[0]) % 64
+    return np.pad(x, ((0, pad), (0, 0))).reshape(-1, 64, x.shape[1]).max(1)
+
+
+# Heidelberger-Welch: the second-half mcse, two sweeps from row 0 for every candidate window,
+# then the mcse of each series' chosen window (IMSE block sweeps as above, windows of mixed length)
+starts, i_final = mb.diag.heidel_starts(n)
+chosen = hd[:, 0, :].T.astype(np.int64)                            # Burn-in = i + start - 2 = the 0-based start at start = 1
+chosen = np.where(hd[:, 1, :].T > 0, chosen, starts[-1])           # not converged: the last window tested
+terms = eng.chain_mcse_from(chosen, n, "imse")[:, :, mb.diag.F_TERMS]
+examined = np.minimum(terms + 2, (n - chosen - 2) // 2 + 1)
+hw = per_wave(np.ceil(examined / DG_PAIRS))
+heidel = {"candidates": starts, "cvm_passes": 2, "cvm_bytes": 2 * (n - starts[0]) * eng.pmon * a.chains * 8,
+          "not_converged": float((hd[:, 1, :] == 0).mean()), "chosen_start_mean": float(chosen.mean()),
+          "chosen_window_bytes": int((n - chosen).sum()) * 8,
+          "mcse_from_sweeps_wave_mean": float(hw.mean()), "mcse_from_sweeps_wave_max": int(hw.max()),
+          "test_passed": float(np.nanmean(hd[:, 5, :]))}
+
+# Raftery-Lewis: 64 / DG_RF_BITS selection sweeps (+ 1 for the upper order statistic when the
+# quantile index is fractional), then thinning sweeps kthin = 1 .. the wavefront's largest
+DG_RF_BITS = 4
+rfc = eng.chain_raftery(RQ)
+kthin = np.nan_to_num(rfc[:, :, 1], nan=float(n // 2))
+kw = per_wave(kthin)
+sel = 64 // DG_RF_BITS + int(1.0 + (n - 1) * RQ != np.floor(1.0 + (n - 1) * RQ))
+harm = np.array([sum(1.0 / k for k in range(1, int(x) + 1)) for x in kw.ravel()])
+raftery = {"q": RQ, "r": RR, "s": RS, "selection_sweeps": sel,
+           "kthin_lane_mean": float(kthin.mean()), "kthin_lane_max": int(kthin.max()),
+           "thinning_sweeps_wave_mean": float(kw.mean()), "thinning_sweeps_wave_max": int(kw.max()),
+           "thinning_rows_wave_mean_passes": float(harm.mean()),
+           "passes_wave_mean": float(sel + harm.mean()), "ran_out": int(np.isnan(rfc[:, :, 1]).sum()),
+           "dependence_factor_median": float(np.nanmedian(rf[:, 4, :]))}
+
 print(json.dumps({"draws_bytes": nbytes, "kept": n, "chains": a.chains,
                   "autocor_s": t_ac, "changerate_s": t_cr, "gewekediag_imse_s": t_gw, "summarystats_s": t_ss,
+                  "heideldiag_imse_s": t_hd, "rafterydiag_s": t_rf, "heidel": heidel, "raftery": raftery,
                   "imse_blocks": imse, "changerate": cr.tolist(),
                   "autocor_mean": np.nanmean(ac, axis=2).tolist(),
                   "geweke_abs_z_gt_2": float(np.nanmean(np.abs(gw[:, 0, :]) > 2.0)),
