@@ -346,6 +346,37 @@ int mmb_chain_summary(mmb_engine* e, const double* shift /* p */, int64_t batch_
 int mmb_order_hist(mmb_engine* e, int param, int ntargets, const uint64_t* prefix, int pass,
                    uint64_t* counts /* ntargets x 256 */);
 
+/* Highest-posterior-density interval of one monitored param, pooled over chains: hpd(x; alpha)
+ * (src/output/stats.jl:54-74) sorts the N pooled draws, takes a = y[1:m] and
+ * b = y[N-m+1:N], m = max(1, ceil(alpha N)), and returns [a[i], b[i]] at the first minimum of b - a.
+ * Only the m smallest and the m largest values are looked at, so the device sorts those alone
+ * (hpd.hip).  The caller selects the thresholds lo = y[m-1], hi = y[N-m] (0-based) with
+ * mmb_order_hist, then:
+ * mmb_hpd_collect (stats.jl:54-74, the tails of y = sort(x)): one pass over the kept draws of
+ *   `param` appends the values strictly below lo to the engine's "below" buffer and those
+ *   strictly above hi to its "above" buffer, in the order of the radix select's key (which puts
+ *   -0.0 below +0.0), unsorted.  counts = the two numbers found.  Nothing is written past `cap`
+ *   elements of either buffer (the buffers grow to cap on demand; a correct call passes m - 1); a
+ *   count above cap is MMB_E_ARG and leaves the engine without tails.
+ * mmb_hpd_get_tails (stats.jl:54-74): copies the first nbelow / nabove elements of the two
+ *   buffers out, for the all-gather of a sharded summary; the counts are the caller's, as
+ *   mmb_hpd_collect returned them, and at most the buffers' capacity (elements past the last
+ *   collect's counts hold whatever earlier calls left there).  Sorted once mmb_hpd_gap ran.
+ * mmb_hpd_set_tails (stats.jl:54-74): the inverse: uploads tails (the pooled ones of every rank)
+ *   as the engine's tails, in any order.
+ * mmb_hpd_gap (stats.jl:58-63): sorts both tails ascending on the device (LSD radix sort on the
+ *   64-bit key), then takes the first minimum of d[i] = b[i] - a[i], i < m, over the virtual arrays
+ *   a = sorted below, then copies of lo;  b = copies of hi, then sorted above (each m long; the
+ *   copies are never stored).  out = [a[i], b[i]], *index = i (0-based).  `total` is N, the pooled
+ *   number of draws: 1 <= m <= total, both counts <= m - 1, and lo <= hi unless the tails overlap
+ *   (2m > total); else MMB_E_ARG.  Needs tails (mmb_hpd_collect or mmb_hpd_set_tails): else
+ *   MMB_E_STATE.
+ * NaN draws: the key puts them at the extremes; the interval is then unspecified. */
+int mmb_hpd_collect(mmb_engine* e, int param, double lo, double hi, int64_t cap, int64_t counts[2]);
+int mmb_hpd_get_tails(mmb_engine* e, double* below, int64_t nbelow, double* above, int64_t nabove);
+int mmb_hpd_set_tails(mmb_engine* e, const double* below, int64_t nbelow, const double* above, int64_t nabove);
+int mmb_hpd_gap(mmb_engine* e, int64_t m, int64_t total, double lo, double hi, double out[2], int64_t* index);
+
 /* Upload draws: the inverse of mmb_get_draws.  `draws` is nkept x p x K column-major (the
  * Chains value layout, iteration fastest); it is transposed into the device draw buffer, which
  * grows by mmb_reserve_draws' rule, and becomes the engine's kept window (mmb_num_kept ==

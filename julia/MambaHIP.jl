@@ -131,6 +131,58 @@ function chain_raftery(e, q::Real)
   check(ccall((:mmb_chain_raftery, libmambahip), Cint, (Ptr{Void}, Cdouble, Ptr{Float64}), e, q, out), e); out
 end
 
+# hpd(c; alpha) (stats.jl:54-74) of one engine's device-kept draws, pooled over its chains: the
+# thresholds y[m] and y[N-m+1] by the radix select on the order-preserving key (mmb_order_hist, 8
+# one-byte passes), then the draws beyond them are collected, sorted and reduced to the first
+# minimum of b - a on the device (mmb_hpd_*); params and ranks are 0-based at the ABI
+function order_hist(e, param::Integer, prefix::Vector{UInt64}, pass::Integer)
+  out = zeros(UInt64, 256, length(prefix))
+  check(ccall((:mmb_order_hist, libmambahip), Cint, (Ptr{Void}, Cint, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}),
+              e, param, length(prefix), prefix, pass, out), e); out
+end
+key_to_double(k::UInt64) = reinterpret(Float64, (k >> 63) == 1 ? k & ~(UInt64(1) << 63) : ~k)
+function order_stat(e, param::Integer, rank::Integer)
+  prefix, rem = UInt64(0), Int64(rank)
+  for pass in 0:7
+    h = order_hist(e, param, [prefix], pass)
+    d = 0
+    while rem >= Int64(h[d + 1, 1])
+      rem -= Int64(h[d + 1, 1]); d += 1
+    end
+    prefix = (prefix << 8) | UInt64(d)
+  end
+  key_to_double(prefix)
+end
+function hpd_collect(e, param::Integer, lo::Real, hi::Real, cap::Integer)
+  counts = zeros(Int64, 2)
+  check(ccall((:mmb_hpd_collect, libmambahip), Cint, (Ptr{Void}, Cint, Cdouble, Cdouble, Int64, Ptr{Int64}),
+              e, param, lo, hi, cap, counts), e); counts
+end
+function hpd_get_tails(e, nbelow::Integer, nabove::Integer)
+  below, above = zeros(Float64, nbelow), zeros(Float64, nabove)
+  check(ccall((:mmb_hpd_get_tails, libmambahip), Cint, (Ptr{Void}, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+              e, below, nbelow, above, nabove), e); below, above
+end
+hpd_set_tails!(e, below::Vector{Float64}, above::Vector{Float64}) =
+  check(ccall((:mmb_hpd_set_tails, libmambahip), Cint, (Ptr{Void}, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+              e, below, length(below), above, length(above)), e)
+function hpd_gap(e, m::Integer, total::Integer, lo::Real, hi::Real)
+  out, idx = zeros(Float64, 2), zeros(Int64, 1)
+  check(ccall((:mmb_hpd_gap, libmambahip), Cint, (Ptr{Void}, Int64, Int64, Cdouble, Cdouble, Ptr{Float64}, Ptr{Int64}),
+              e, m, total, lo, hi, out, idx), e); out, idx[1]
+end
+function hpd(e; alpha::Real=0.05)                 # p x 2: [lower, upper] per monitored param
+  N = Int64(num_kept(e)) * Int64(num_chains(e))
+  m = max(1, ceil(Int, alpha * N))
+  vals = zeros(Float64, Int(num_monitored(e)), 2)
+  for j in 1:size(vals, 1)
+    lo, hi = order_stat(e, j - 1, m - 1), order_stat(e, j - 1, N - m)
+    hpd_collect(e, j - 1, lo, hi, m - 1)
+    vals[j, :] = hpd_gap(e, m, N, lo, hi)[1]
+  end
+  vals
+end
+
 # the one collective (mmb_comm_*): RCCL over xGMI inside the library
 function comm_id()
   id = zeros(UInt8, MMB_COMM_ID_BYTES)

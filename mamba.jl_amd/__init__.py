@@ -12,7 +12,7 @@ from .gelman import (Comm, cor_from_sums, cor_sharded, gelmandiag, gelmandiag_rc
                      psrf_from_sums)
 from .diag import (autocor, changerate_sharded, geweke_windows, geweke_z, gewekediag, heideldiag,  # noqa: F401
                    pcramer, rafterydiag)
-from .summary import pool_summary, quantile_sharded, summarystats_sharded  # noqa: F401
+from .summary import hpd_sharded, pool_summary, quantile_sharded, summarystats_sharded  # noqa: F401
 from .mcmc import Chains, Engine, mcmc, mcmc_restart, read, write  # noqa: F401
 from .model import line, logistic, rats  # noqa: F401
 from .samplers import (AMM, AMWG, HMC, MALA, NUTS, ArgumentError, Gibbs, Multivariate, Sampler,  # noqa: F401

@@ -123,6 +123,10 @@ def _declare(lib):
         "mmb_gr_partials": (C.c_int, [P, C.POINTER(I32), D, D]),
         "mmb_chain_summary": (C.c_int, [P, D, I64, I64, D]),
         "mmb_order_hist": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64)]),
+        "mmb_hpd_collect": (C.c_int, [P, C.c_int, C.c_double, C.c_double, I64, C.POINTER(I64)]),
+        "mmb_hpd_get_tails": (C.c_int, [P, D, I64, D, I64]),
+        "mmb_hpd_set_tails": (C.c_int, [P, D, I64, D, I64]),
+        "mmb_hpd_gap": (C.c_int, [P, I64, I64, C.c_double, C.c_double, D, C.POINTER(I64)]),
         "mmb_sync": (C.c_int, [P]),
         "mmb_kernel_time": (C.c_int, [P, D, C.POINTER(I64), C.POINTER(I64)]),
         "mmb_state_bytes": (C.c_int, [P, D]),

@@ -51,6 +51,17 @@ hipError_t mmb_launch_chain_mcse_from(int P, int K, const int64_t* i0s, int64_t 
                                       const double* draws, double* out, hipStream_t st);
 hipError_t mmb_launch_chain_raftery(int P, int K, int64_t n, int64_t rlo, int interp, double h, const double* draws,
                                     double* out, hipStream_t st);
+// hpd.hip
+uint64_t mmb_hpd_key(double x);
+double mmb_hpd_unkey(uint64_t key);
+int64_t mmb_hpd_tiles(int64_t n);
+hipError_t mmb_launch_hpd_collect(int P, int j, int64_t n, int K, const double* draws, double lo, double hi,
+                                  int64_t cap, uint64_t* below, uint64_t* above, unsigned long long* meta,
+                                  hipStream_t st);
+hipError_t mmb_launch_hpd_sort(uint64_t* keys, uint64_t* tmp, int64_t n, uint64_t varying, unsigned int* tilehist,
+                               unsigned long long* ghist, int* in_tmp, hipStream_t st);
+hipError_t mmb_launch_hpd_gap(const uint64_t* below, int64_t nb, const uint64_t* above, int64_t na, int64_t m,
+                              double lo, double hi, double* part_d, long long* part_i, double* res, hipStream_t st);
 
 hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
 
@@ -129,6 +140,15 @@ struct mmb_engine {
   double* d_draws = nullptr;
   size_t draws_cap = 0;
   int64_t n_kept = 0;
+  // hpd tails (mmb_hpd_*): keys of the draws below / above the thresholds, a sort buffer as large and
+  // the sort's tile histograms, all for hpd_cap keys; grown on demand, freed in mmb_destroy
+  uint64_t *hpd_below = nullptr, *hpd_above = nullptr, *hpd_tmp = nullptr;
+  unsigned int* hpd_tilehist = nullptr;
+  unsigned long long* hpd_words = nullptr;  // meta, ghist, gap partials and result (HPD_WORDS)
+  int64_t hpd_cap = 0;
+  int64_t hpd_n[2] = {0, 0};                // keys held: below, above
+  uint64_t hpd_varying[2] = {0, 0};         // bits in which each buffer's keys differ (sort passes to run)
+  bool hpd_have = false, hpd_sorted = false;
   // node IR (MMB_MODEL_IR): host copies of the lowered model, device tables
   std::vector<mmb_ir_node> ir_nodes;
   std::vector<int32_t> ir_code, ir_mon;
@@ -901,6 +921,11 @@ void mmb_destroy(mmb_engine* e) {
 #endif
   free_dev(e);
   if (e->d_data) (void)hipFree(e->d_data);
+  {
+    void* hp[] = {e->hpd_below, e->hpd_above, e->hpd_tmp, e->hpd_tilehist, e->hpd_words};
+    for (void* q : hp)
+      if (q) (void)hipFree(q);
+  }
   {
     void* ip[] = {e->d_ir_nodes, e->d_ir_code, e->d_ir_mon, e->d_ir_const, e->d_ir_pool, e->d_ir_blocks};
     for (void* q : ip)
@@ -2126,6 +2151,159 @@ int mmb_order_hist(mmb_engine* e, int param, int ntargets, const uint64_t* prefi
   (void)hipFree(dp);
   (void)hipFree(dc);
   if (st != hipSuccess) return fail(e, MMB_E_HIP, "order_hist: %s", hipGetErrorString(st));
+  return 0;
+}
+
+// ---------------------------------------------------------------- hpd (stats.jl:54-74)
+// hpd_words: the collect pass's counts and key bits, the sort's digit totals, the gap's partials and result
+constexpr int HPD_W_META = 0, HPD_W_GHIST = 8, HPD_W_PARTD = 264, HPD_W_PARTI = 520, HPD_W_RES = 776,
+              HPD_WORDS = 784;
+constexpr int64_t HPD_MAX_KEYS = 0xffffffffll;  // the sort's scatter offsets are 32-bit
+
+// room for `cap` keys in each tail and in the sort buffer; growing drops the tails held
+static int hpd_reserve(mmb_engine* e, int64_t cap) {
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->hpd_words) HIPCHK(e, dalloc(&e->hpd_words, (size_t)HPD_WORDS));
+  if (cap <= e->hpd_cap) return 0;
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // the old buffers may still be read by a kernel
+  void* old[] = {e->hpd_below, e->hpd_above, e->hpd_tmp, e->hpd_tilehist};
+  for (void* q : old)
+    if (q) (void)hipFree(q);
+  e->hpd_below = e->hpd_above = e->hpd_tmp = nullptr;
+  e->hpd_tilehist = nullptr;
+  e->hpd_cap = 0;
+  e->hpd_have = false;
+  hipError_t st = dalloc(&e->hpd_below, (size_t)cap);
+  if (st == hipSuccess) st = dalloc(&e->hpd_above, (size_t)cap);
+  if (st == hipSuccess) st = dalloc(&e->hpd_tmp, (size_t)cap);
+  if (st == hipSuccess) st = dalloc(&e->hpd_tilehist, (size_t)256 * mmb_hpd_tiles(cap));
+  if (st != hipSuccess)
+    return fail(e, st == hipErrorOutOfMemory ? MMB_E_NOMEM : MMB_E_HIP, "hpd buffers for %lld values: %s",
+                (long long)cap, hipGetErrorString(st));
+  e->hpd_cap = cap;
+  return 0;
+}
+
+int mmb_hpd_collect(mmb_engine* e, int param, double lo, double hi, int64_t cap, int64_t counts[2]) {
+  if (!e || !counts) return fail(e, MMB_E_ARG, "null argument");
+  if (param < 0 || param >= e->pmon) return fail(e, MMB_E_ARG, "param %d out of range", param);
+  if (cap < 0 || cap > HPD_MAX_KEYS) return fail(e, MMB_E_ARG, "cap must be 0 .. %lld", (long long)HPD_MAX_KEYS);
+  if (lo != lo || hi != hi) return fail(e, MMB_E_ARG, "a threshold is NaN");
+  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  e->hpd_have = e->hpd_sorted = false;
+  if (int rc = hpd_reserve(e, cap)) return rc;
+  unsigned long long* meta = e->hpd_words + HPD_W_META;
+  unsigned long long h[6] = {};
+  hipError_t st = mmb_launch_hpd_collect(e->pmon, param, e->n_kept, (int)e->K, e->d_draws, lo, hi, cap, e->hpd_below,
+                                         e->hpd_above, meta, e->stream);
+  if (st == hipSuccess) st = hipMemcpyAsync(h, meta, sizeof h, hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_collect: %s", hipGetErrorString(st));
+  counts[0] = (int64_t)h[0];
+  counts[1] = (int64_t)h[1];
+  if (counts[0] > cap || counts[1] > cap)
+    return fail(e, MMB_E_ARG, "hpd_collect: %lld draws below lo and %lld above hi, room for %lld each (lo and hi "
+                "must be the order statistics m - 1 and N - m, cap = m - 1)", (long long)counts[0],
+                (long long)counts[1], (long long)cap);
+  for (int b = 0; b < 2; ++b) {
+    e->hpd_n[b] = counts[b];
+    e->hpd_varying[b] = counts[b] > 0 ? (uint64_t)(h[2 + 2 * b] ^ h[3 + 2 * b]) : 0;
+  }
+  e->hpd_have = true;
+  return 0;
+}
+
+int mmb_hpd_get_tails(mmb_engine* e, double* below, int64_t nbelow, double* above, int64_t nabove) {
+  if (!e || (nbelow > 0 && !below) || (nabove > 0 && !above)) return fail(e, MMB_E_ARG, "null argument");
+  if (nbelow < 0 || nabove < 0) return fail(e, MMB_E_ARG, "counts must be >= 0");
+  if (nbelow > e->hpd_cap || nabove > e->hpd_cap)
+    return fail(e, MMB_E_ARG, "counts %lld, %lld exceed the tail buffers' %lld", (long long)nbelow, (long long)nabove,
+                (long long)e->hpd_cap);
+  if (nbelow + nabove == 0) return 0;
+  HIPCHK(e, hipSetDevice(e->device));
+  std::vector<uint64_t> kb((size_t)nbelow), ka((size_t)nabove);
+  hipError_t st = hipSuccess;
+  if (nbelow > 0)
+    st = hipMemcpyAsync(kb.data(), e->hpd_below, kb.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess && nabove > 0)
+    st = hipMemcpyAsync(ka.data(), e->hpd_above, ka.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_get_tails: %s", hipGetErrorString(st));
+  for (int64_t i = 0; i < nbelow; ++i) below[i] = mmb_hpd_unkey(kb[(size_t)i]);
+  for (int64_t i = 0; i < nabove; ++i) above[i] = mmb_hpd_unkey(ka[(size_t)i]);
+  return 0;
+}
+
+int mmb_hpd_set_tails(mmb_engine* e, const double* below, int64_t nbelow, const double* above, int64_t nabove) {
+  if (!e || (nbelow > 0 && !below) || (nabove > 0 && !above)) return fail(e, MMB_E_ARG, "null argument");
+  if (nbelow < 0 || nabove < 0) return fail(e, MMB_E_ARG, "counts must be >= 0");
+  if (nbelow > HPD_MAX_KEYS || nabove > HPD_MAX_KEYS)
+    return fail(e, MMB_E_ARG, "at most %lld values per tail", (long long)HPD_MAX_KEYS);
+  e->hpd_have = e->hpd_sorted = false;
+  if (int rc = hpd_reserve(e, std::max(nbelow, nabove))) return rc;
+  const double* src[2] = {below, above};
+  const int64_t cnt[2] = {nbelow, nabove};
+  uint64_t* dst[2] = {e->hpd_below, e->hpd_above};
+  std::vector<uint64_t> keys[2];
+  hipError_t st = hipSuccess;
+  for (int b = 0; b < 2 && st == hipSuccess; ++b) {
+    keys[b].resize((size_t)cnt[b]);
+    uint64_t bor = 0, band = ~0ull;
+    for (int64_t i = 0; i < cnt[b]; ++i) {
+      const uint64_t k = mmb_hpd_key(src[b][i]);
+      keys[b][(size_t)i] = k;
+      bor |= k;
+      band &= k;
+    }
+    e->hpd_varying[b] = cnt[b] > 0 ? bor ^ band : 0;
+    if (cnt[b] > 0)
+      st = hipMemcpyAsync(dst[b], keys[b].data(), keys[b].size() * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream);
+  }
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);  // the host copies go out of scope
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_set_tails: %s", hipGetErrorString(st));
+  e->hpd_n[0] = nbelow;
+  e->hpd_n[1] = nabove;
+  e->hpd_have = true;
+  return 0;
+}
+
+int mmb_hpd_gap(mmb_engine* e, int64_t m, int64_t total, double lo, double hi, double out[2], int64_t* index) {
+  if (!e || !out || !index) return fail(e, MMB_E_ARG, "null argument");
+  if (m < 1 || m > total) return fail(e, MMB_E_ARG, "need 1 <= m <= total, got m = %lld, total = %lld", (long long)m,
+                                      (long long)total);
+  if (lo != lo || hi != hi) return fail(e, MMB_E_ARG, "a threshold is NaN");
+  if (lo > hi && m <= total - m)
+    return fail(e, MMB_E_ARG, "lo = %g > hi = %g although the tails do not overlap (2 m <= total)", lo, hi);
+  if (!e->hpd_have) return fail(e, MMB_E_STATE, "no tails: call mmb_hpd_collect or mmb_hpd_set_tails first");
+  if (e->hpd_n[0] > m - 1 || e->hpd_n[1] > m - 1)
+    return fail(e, MMB_E_ARG, "the tails hold %lld and %lld values, more than m - 1 = %lld", (long long)e->hpd_n[0],
+                (long long)e->hpd_n[1], (long long)(m - 1));
+  HIPCHK(e, hipSetDevice(e->device));
+  hipError_t st = hipSuccess;
+  if (!e->hpd_sorted) {
+    uint64_t** buf[2] = {&e->hpd_below, &e->hpd_above};
+    for (int b = 0; b < 2 && st == hipSuccess; ++b) {
+      int in_tmp = 0;
+      st = mmb_launch_hpd_sort(*buf[b], e->hpd_tmp, e->hpd_n[b], e->hpd_varying[b], e->hpd_tilehist,
+                               e->hpd_words + HPD_W_GHIST, &in_tmp, e->stream);
+      if (st == hipSuccess && in_tmp) std::swap(*buf[b], e->hpd_tmp);  // equal capacities: the buffers trade places
+    }
+    if (st != hipSuccess) {
+      e->hpd_have = false;  // a buffer may be half sorted
+      return fail(e, MMB_E_HIP, "hpd sort: %s", hipGetErrorString(st));
+    }
+    e->hpd_sorted = true;
+  }
+  unsigned long long h[3] = {};
+  double* res = (double*)(e->hpd_words + HPD_W_RES);
+  st = mmb_launch_hpd_gap(e->hpd_below, e->hpd_n[0], e->hpd_above, e->hpd_n[1], m, lo, hi,
+                          (double*)(e->hpd_words + HPD_W_PARTD), (long long*)(e->hpd_words + HPD_W_PARTI), res,
+                          e->stream);
+  if (st == hipSuccess) st = hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_gap: %s", hipGetErrorString(st));
+  memcpy(out, h, 2 * sizeof(double));
+  *index = (int64_t)h[2];
   return 0;
 }
 

@@ -216,6 +216,37 @@ class Engine:
                                           out.ctypes.data_as(u64)))
         return out
 
+    # hpd (stats.jl:54-74) on the device-kept draws: summary.hpd_sharded drives these
+    def hpd_collect(self, param, lo, hi, cap):
+        """Collect the kept draws of `param` strictly below `lo` and strictly above `hi` into the
+        engine's two tail buffers (mmb_hpd_collect), at most `cap` each: (n_below, n_above).  A
+        count above `cap` is an error, and nothing is written past `cap`."""
+        counts = (C.c_int64 * 2)()
+        self._chk(self.lib.mmb_hpd_collect(self.h, int(param), float(lo), float(hi), int(cap), counts))
+        return int(counts[0]), int(counts[1])
+
+    def hpd_get_tails(self, nbelow, nabove):
+        """The first `nbelow` / `nabove` values of the tail buffers (mmb_hpd_get_tails), as collected:
+        unsorted until hpd_gap has run."""
+        below, above = np.empty(int(nbelow)), np.empty(int(nabove))
+        self._chk(self.lib.mmb_hpd_get_tails(self.h, abi.dptr(below), below.size, abi.dptr(above), above.size))
+        return below, above
+
+    def hpd_set_tails(self, below, above):
+        """Upload tails (the pooled ones of every rank) as the engine's tails (mmb_hpd_set_tails)."""
+        below = np.ascontiguousarray(below, dtype=np.float64).reshape(-1)
+        above = np.ascontiguousarray(above, dtype=np.float64).reshape(-1)
+        self._chk(self.lib.mmb_hpd_set_tails(self.h, abi.dptr(below), below.size, abi.dptr(above), above.size))
+
+    def hpd_gap(self, m, total, lo, hi):
+        """Sort the tails on the device and take the first minimum of b - a over a = sorted below
+        padded with `lo` and b = `hi` padding then sorted above, `m` each (mmb_hpd_gap; `total` the
+        pooled number of draws): (array [a[i], b[i]], i)."""
+        out = np.empty(2)
+        idx = C.c_int64()
+        self._chk(self.lib.mmb_hpd_gap(self.h, int(m), int(total), float(lo), float(hi), abi.dptr(out), C.byref(idx)))
+        return out, int(idx.value)
+
     def set_draws(self, value):
         """Upload `value` (n x p x chains, the Chains layout) as the device-kept draws
         (mmb_set_draws, the inverse of `draws`): the device summaries then run on it."""
@@ -317,6 +348,14 @@ class Chains:
         """quantile(c; q) (stats.jl:73-80), pooled over iterations and chains: p x len(q)."""
         from .summary import quantile_sharded
         return quantile_sharded(self._device_engine(), q)
+
+    def hpd(self, alpha=0.05):
+        """hpd(c; alpha) (stats.jl:66-74): the highest-posterior-density interval of each monitored
+        param, draws pooled over iterations and chains: (p x 2 array, ["95% Lower", "95% Upper"]).
+        The tails are sorted on the device; only the result leaves it.  NaN draws are not
+        detected: the result is then unspecified."""
+        from .summary import hpd_labels, hpd_sharded
+        return hpd_sharded(self._device_engine(), alpha), hpd_labels(alpha)
 
     def describe(self, q=(0.025, 0.25, 0.5, 0.75, 0.975), batch_size=100):
         """describe(c) (stats.jl:42-52): summarystats and quantiles per monitored name."""

@@ -14,10 +14,14 @@ iterations AND chains.  The per-element work runs on the GPU (summary.hip):
 * quantile: exact order statistics by radix select (mmb_order_hist, 8 passes of one byte,
   counts all-reduced across GPUs), then Julia 0.5 Base.quantile's interpolation
   (index = 1 + (N-1)q, r = (1-h) v[lo] + h v[hi]; recalled from Julia Base, not vendored).
+* hpd (src/output/stats.jl:54-74): the two thresholds by the same radix select, then the draws
+  beyond them are collected, sorted and reduced on the device (hpd.hip, mmb_hpd_*).
 
 The cross-GPU reductions are callbacks (`allreduce_sum`, `allgather`), identity on one
 engine; bench.py / tests pass torch.distributed ones (RCCL or gloo).
 """
+import math
+
 import numpy as np
 
 from .samplers import ArgumentError
@@ -170,3 +174,52 @@ def quantile_sharded(engine, q=QUANTILES, allreduce_sum=None):
             a, b = v[lo[t] - 1], v[hi[t] - 1]
             out[j, t] = a if index[t] == lo[t] else (1.0 - h[t]) * a + h[t] * b
     return out
+
+
+# ---- highest-posterior-density intervals: device tail sort ------------------------------
+def hpd_count(alpha, N):
+    """m of hpd(x; alpha) (stats.jl:56): max(1, ceil(Int, alpha * N)) on the double product."""
+    alpha = float(alpha)
+    if not (math.isfinite(alpha) and alpha < 1.0):
+        raise ArgumentError(f"alpha must be finite and < 1, got {alpha}")
+    return max(1, math.ceil(alpha * float(N)))
+
+
+def hpd_labels(alpha):
+    """The column labels of hpd(c; alpha) (stats.jl:67-68): 100 (1 - alpha) as showoff prints it,
+    "95% Lower" / "95% Upper" (97.5 stays 97.5)."""
+    pct = f"{100.0 * (1.0 - float(alpha)):.10g}"
+    return [f"{pct}% Lower", f"{pct}% Upper"]
+
+
+def hpd_sharded(engine, alpha=0.05, allreduce_sum=None, allgather=None, return_index=False):
+    """hpd(c; alpha) (stats.jl:54-74) pooled over iterations and all chains: p x 2 [lower, upper]
+    (with return_index also the 0-based index i of the first minimum of b - a, per param).
+
+    Of y = sort(x) only a = y[:m] and b = y[N-m:] are looked at.  The thresholds y[m-1] and
+    y[N-m] come from one radix select (order_stats); one pass collects the draws strictly below
+    the first and strictly above the second (at most m - 1 each: the rest of a and b are copies
+    of the thresholds), the device sorts both and reduces b - a to its first minimum
+    (hpd.hip).  With `allgather` (one engine per rank) every rank gathers the tails of all
+    ranks, uploads the pooled ones and runs the same device sort and reduction, so all ranks get
+    the same answer; alone, nothing but the result leaves the device.  alpha <= 0 gives m = 1:
+    [min, max].  alpha > 0.5 lets the two tails overlap, which the padding covers.  NaN draws
+    are not detected (the key puts them at the extremes): the result is then unspecified."""
+    n = engine.num_kept()
+    N = n * _global_chains(engine, allreduce_sum)
+    m = hpd_count(alpha, N)
+    out = np.empty((engine.pmon, 2))
+    index = np.empty(engine.pmon, dtype=np.int64)
+    for j in range(engine.pmon):
+        lo, hi = (float(v) for v in order_stats(engine, j, [m - 1, N - m], allreduce_sum))
+        nb, na = engine.hpd_collect(j, lo, hi, m - 1)
+        if allgather is not None:
+            parts = allgather(engine.hpd_get_tails(nb, na))
+            below = np.concatenate([np.asarray(a[0], dtype=np.float64) for a in parts])
+            above = np.concatenate([np.asarray(a[1], dtype=np.float64) for a in parts])
+            if below.size > m - 1 or above.size > m - 1:
+                raise RuntimeError(f"hpd: pooled tails of {below.size} and {above.size} values, expected at most "
+                                   f"{m - 1}")
+            engine.hpd_set_tails(below, above)
+        out[j], index[j] = engine.hpd_gap(m, N, lo, hi)
+    return (out, index) if return_index else out

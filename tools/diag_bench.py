@@ -11,6 +11,9 @@ defaults Nmin = 3746 exceeds the 2000 kept draws and no kernel would run): the w
 passes each kernel's algorithm makes over its window, and per wavefront the sweeps of the
 Raftery-Lewis selection (fixed by the digit width) and of its thinning loop (a wavefront sweeps
 until its last lane's bic is negative; the sweep at kthin reads every kthin-th row).
+For hpd(alpha = 0.05): the wall time of Chains.hpd, of quantile beside it, the sizes of the tails the
+device sorts, and the route a user had without it (download the draws, np.sort each param, the gap
+on the host).
 Run under `rocprofv3 --kernel-trace --stats` for per-kernel durations.
 """
 import argparse
@@ -115,7 +118,35 @@ raftery = {"q": RQ, "r": RR, "s": RS, "selection_sweeps": sel,
            "passes_wave_mean": float(sel + harm.mean()), "ran_out": int(np.isnan(rfc[:, :, 1]).sum()),
            "dependence_factor_median": float(np.nanmedian(rf[:, 4, :]))}
 
-print(json.dumps({"draws_bytes": nbytes, "kept": n, "chains": a.chains,
+# hpd(alpha = 0.05): 8 select passes + 1 collect pass over each param's draws, then the sort of the
+# two tails (2 x (m - 1) keys, the digit passes in which the keys differ) and the gap reduction;
+# quantile (the same select, 10 ranks) beside it, and the route a user had before: download the
+# draws, np.sort each param, the gap on the host (a baseline, not the code under test)
+sim = mb.Chains(np.empty((n, eng.pmon, 0)), m.monitor_names, 1, 1, np.arange(1, a.chains + 1), m, eng)
+t_hpd, (hp, _) = timed(lambda: sim.hpd(0.05))
+t_q, _ = timed(lambda: mb.quantile_sharded(eng))
+N = n * a.chains
+m_hpd = mb.summary.hpd_count(0.05, N)
+tails = []
+for j in range(eng.pmon):
+    lo_j, hi_j = (float(v) for v in mb.summary.order_stats(eng, j, [m_hpd - 1, N - m_hpd]))
+    tails.append(list(eng.hpd_collect(j, lo_j, hi_j, m_hpd - 1)))
+t0 = time.perf_counter()
+val = eng.draws()
+t_dl = time.perf_counter() - t0
+host = np.empty((eng.pmon, 2))
+for j in range(eng.pmon):
+    y = np.sort(val[:, j, :].ravel())
+    d = y[N - m_hpd:] - y[:m_hpd]
+    i = int(np.argmin(d))
+    host[j] = y[i], y[N - m_hpd + i]
+t_host = time.perf_counter() - t0
+del val
+hpd = {"alpha": 0.05, "m": m_hpd, "param_bytes": nbytes // eng.pmon, "tail_counts": tails, "hpd_s": t_hpd,
+       "quantile_s": t_q, "host_route_s": t_host, "host_download_s": t_dl, "host_sort_gap_s": t_host - t_dl,
+       "equals_host_route": bool(np.array_equal(hp, host)), "hpd": hp.tolist()}
+
+print(json.dumps({"draws_bytes": nbytes, "kept": n, "chains": a.chains, "hpd": hpd,
                   "autocor_s": t_ac, "changerate_s": t_cr, "gewekediag_imse_s": t_gw, "summarystats_s": t_ss,
                   "heideldiag_imse_s": t_hd, "rafterydiag_s": t_rf, "heidel": heidel, "raftery": raftery,
                   "imse_blocks": imse, "changerate": cr.tolist(),
