@@ -909,10 +909,10 @@ void mmb_destroy(mmb_engine* e) {
     unsigned long long h[32] = {};
     if (hipModuleGetGlobal(&p, &nb, e->jit_mod, "mmb_prof") == hipSuccess && nb >= sizeof h &&
         hipMemcpyDtoH(h, p, sizeof h) == hipSuccess) {
-      const char* names[] = {"-", "amm:load m/fl/Mv", "amm:proposal", "amm:logf x2+accept", "amm:moments+Sigma",
+      const char* names[] = {"amm:prep", "amm:load m/fl/Mv", "amm:proposal", "amm:logf x2+accept", "amm:moments+Sigma",
                              "amm:pchol", "amm:store", "gibbs", "iteration", "count", "pchol:steps",
                              "pchol:carry", "pchol:writeback", "amwg", "slice", "draws"};
-      for (int i = 1; i < 16; ++i) fprintf(stderr, "MMB_PROF %-22s %llu\n", names[i], h[i]);
+      for (int i = 0; i < 16; ++i) fprintf(stderr, "MMB_PROF %-22s %llu\n", names[i], h[i]);
     }
   }
 #ifdef MMB_PHASE_PROF

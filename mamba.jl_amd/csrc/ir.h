@@ -378,7 +378,10 @@ struct Mdl<MMB_MODEL_IR> {
 #define MMB_IR_SLICE_NC 4
 #endif
   static constexpr int SLICE_NC = MMB_IR_SLICE_NC;  // candidates per round (ir_jit.cpp: 2 or 4)
-  __device__ __forceinline__ static Prep prep(const DBlock&, const St&) { return Prep{}; }
+  struct PrepCache {};  // (rats: the vector blocks' constants kept across blocks)
+  __device__ __forceinline__ static PrepCache prep_cache(double*) { return PrepCache{}; }
+  __device__ __forceinline__ static void prep_wrote(PrepCache&, const DBlock&) {}
+  __device__ __forceinline__ static Prep prep(const DBlock&, const St&, const Grp<G>&, PrepCache&) { return Prep{}; }
   // logpdf!(m, x, block, transform)
   __device__ MMB_IR_LOGF_ATTR static double logf(const SweepArgs& A, const DBlock& B, const St& s, const Lc&, const Grp<G>& g,
                                 const double* x) {

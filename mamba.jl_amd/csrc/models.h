@@ -23,7 +23,8 @@ struct Mdl;
 template <>
 struct Mdl<MMB_MODEL_RATS> {
   static constexpr int G = 32, R = 1, DMAX = 30, DP = 32, TP = 480, VS = 72, PMON = 3;
-  static constexpr int LDS_DBL = TP + 4 * DP;  // matrix + 4 vectors (the stash reuses idle ones)
+  static constexpr int PREP_OFF = TP + 4 * DP;  // the vector blocks' scalar constants (prep_pass)
+  static constexpr int LDS_DBL = PREP_OFF + 8;  // matrix + 4 vectors (the stash reuses idle ones) + constants
   struct St { double a[R], b[R]; double s2c, mua, s2a, mub, s2b; };
   struct Lc { int dummy; };
   __device__ __forceinline__ static int elem(int r, int lane) { return r * G + lane; }
@@ -238,9 +239,62 @@ struct Mdl<MMB_MODEL_RATS> {
     epsm = mag + fabs(dp) + c.invv * fabs(ds) + fabs(del);
     bad = bad || !isfinite(c.invv) || !isfinite(c.yk);
   }
-  // block-update-invariant context (vector blocks); scalar blocks fall back to logf
+  // block-update-invariant context (vector blocks); scalar blocks fall back to logf.
+  // vec_ctx's scalars are functions of one variance node each -- (sig, logsig) of s2_alpha or
+  // s2_beta, (invv, yk) of s2_c -- and all 32 lanes of the group would form the same numbers, so
+  // one pass forms them for both vector nodes at once, a variance node per lane (0: s2_alpha,
+  // 1: s2_beta, 2 and the idle lanes: s2_c): one sqrt, one mmb_log and one division issued where
+  // two vec_ctx calls issue four, four and two.  Each lane applies to its node the operations
+  // vec_ctx applies, in the same order, so the values are the same bits.  They are kept in the
+  // chain's LDS region, pp = [sig_a, logsig_a | sig_b, logsig_b | invv, yk], which no block
+  // update touches, and a vector block reads its four with two 16-byte broadcast reads.
+  // Validity: one stale bit per variance node (wave-uniform: it depends on the descriptors
+  // only).  All are set where the kernel starts, so nothing is carried over a launch or a host
+  // write; after every block of the sweep, prep_wrote sets the bits of the variance nodes the
+  // block's descriptor holds, whatever its sampler.  A vector block whose own variance or s2_c
+  // is stale runs the pass, which refreshes all three: in Gibbs+AMM (s2_c, alpha, mu_alpha,
+  // s2_alpha, beta, mu_beta, s2_beta) alpha's update runs it and beta's finds s2_beta and s2_c
+  // fresh -- one pass per iteration.
   using Prep = VecCtx;
-  __device__ __forceinline__ static Prep prep(const DBlock& B, const St& s) { return vec_ctx(B, s); }
+  struct PrepCache { double* pp; unsigned stale; };
+  __device__ __forceinline__ static PrepCache prep_cache(double* lds) { return PrepCache{lds + PREP_OFF, 7u}; }
+  __device__ __forceinline__ static unsigned prep_bit(int node) {
+    return node == MMB_RATS_S2_ALPHA ? 1u : node == MMB_RATS_S2_BETA ? 2u : node == MMB_RATS_S2_C ? 4u : 0u;
+  }
+  __device__ __forceinline__ static void prep_wrote(PrepCache& k, const DBlock& B) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+      if (a < B.nn) k.stale |= prep_bit(B.nodes[a]);
+  }
+  __device__ __forceinline__ static void prep_pass(const St& s, int lane, double* pp) {
+    const double var = blend(lane == 0, s.s2a, blend(lane == 1, s.s2b, s.s2c));
+    const double sg = sqrt(var);  // vec_ctx's sig (lanes 0, 1) or sc
+    const double value = sg * sg;
+    const double lg = mmb_log(lane < 2 ? sg : value);
+    const double invv = 1.0 / value;
+    const double yk = 150 * MMB_LOG2PI + 150 * lg;
+    if (lane < 3) *(double2*)(pp + 2 * lane) = lane < 2 ? make_double2(sg, lg) : make_double2(invv, yk);
+    grp_sync();
+  }
+  __device__ __forceinline__ static Prep prep(const DBlock& B, const St& s, const Grp<G>& g, PrepCache& k) {
+    VecCtx c;
+    c.al = B.nodes[0] == MMB_RATS_ALPHA;
+    c.mu = c.al ? s.mua : s.mub;
+    if (!is_vec(B.nodes[0])) {  // scalar block: logf_p is logf, nothing reads the context
+      c.sig = c.logsig = c.yk = c.invv = 0.0;
+      return c;
+    }
+    if (k.stale & ((c.al ? 1u : 2u) | 4u)) {
+      prep_pass(s, g.lane, k.pp);
+      k.stale = 0u;
+    }
+    const double2 sl = *(const double2*)(k.pp + (c.al ? 0 : 2)), iy = *(const double2*)(k.pp + 4);
+    c.sig = sl.x;
+    c.logsig = sl.y;
+    c.invv = iy.x;
+    c.yk = iy.y;
+    return c;
+  }
   __device__ __forceinline__ static double logf_p(const SweepArgs& A, const DBlock& B, const Prep& c,
                                                   const St& s, const Lc& l, const Grp<G>& g,
                                                   const double* x) {
@@ -557,7 +611,10 @@ struct Mdl<MMB_MODEL_LINE> {
   struct SCtx {};
   struct SMemo {};
   struct Prep {};
-  __device__ __forceinline__ static Prep prep(const DBlock&, const St&) { return Prep{}; }
+  struct PrepCache {};  // (rats: the vector blocks' constants kept across blocks)
+  __device__ __forceinline__ static PrepCache prep_cache(double*) { return PrepCache{}; }
+  __device__ __forceinline__ static void prep_wrote(PrepCache&, const DBlock&) {}
+  __device__ __forceinline__ static Prep prep(const DBlock&, const St&, const Grp<G>&, PrepCache&) { return Prep{}; }
   __device__ __forceinline__ static double logf_p(const SweepArgs& A, const DBlock& B, const Prep&,
                                                   const St& s, const Lc& l, const Grp<G>& g,
                                                   const double* x) {

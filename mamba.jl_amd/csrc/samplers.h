@@ -126,7 +126,8 @@ struct Smp {
 
   // amwg.jl:68-115 (sample!, setadapt!, amwg_sub!).
   __device__ __forceinline__ static void amwg(const SweepArgs& A, const DBlock& B, int c, const mmb_rng& rn,
-                              const mmb_rng& ru, bool adapt, St& s, const Lc& l, const Grp<G>& g) {
+                              const mmb_rng& ru, bool adapt, St& s, const Lc& l, const Grp<G>& g,
+                              typename M::PrepCache& pk) {
     const int d = B.d;
     double x[R], sig[R], acc[R], z[R];
     M::unlist(B, s, g.lane, x);
@@ -146,7 +147,7 @@ struct Smp {
     fl = adapt ? (fl | 1) : (fl & ~1);
     const double ad = adapt ? 1.0 : 0.0;
     if (adapt) m += 1;
-    const typename M::Prep pc = M::prep(B, s);
+    const typename M::Prep pc = M::prep(B, s, g, pk);
     // the proposal normals and (lane groups) the accept uniforms of every element at once,
     // element e on its own lane: the same Philox draws (index e) the sequential loop below
     // consumes, so the values are bit-identical; each step then takes its uniform from lane e
@@ -718,6 +719,7 @@ struct Smp {
 
   // ---------------------------------------------------------------- AMM
   // amm.jl:66-108.  LDS per chain: mat[TP] | z2[DP] | vv[DP] | mv[DP] | ia[2*DP ints]
+  // (rats: then the vector blocks' scalar constants, models.h prep_pass, which nothing here touches)
   // Carried proposal (32-lane groups, diagonal SigmaL): the proposal of the NEXT iteration,
   // x' - v = SigmaL z1' [beta * . + (1 - beta) SigmaLm z2'] (amm.jl:72-76), depends only on
   // that iteration's draws (Philox keyed by the iteration), the tune m after this update and
@@ -737,7 +739,7 @@ struct Smp {
   __device__ __forceinline__ static void amm(const SweepArgs& A, const DBlock& B, int c, uint32_t chain,
                              int64_t it, int b, const mmb_rng& rn,
                              const mmb_rng& ru, bool adapt, St& s, const Lc& l, const Grp<G>& g,
-                             double* lds, double upre) {
+                             double* lds, double upre, typename M::PrepCache& pk) {
     const int d = B.d;
     const int T = mmb_tri(d);
     double* mat = lds;
@@ -868,7 +870,8 @@ struct Smp {
 #pragma unroll
     for (int r = 0; r < R; ++r) x[r] = x[r] + v[r];
     MMB_PROF_MARK(2, g.lane)
-    const typename M::Prep pc = M::prep(B, s);
+    const typename M::Prep pc = M::prep(B, s, g, pk);
+    MMB_PROF_MARK(0, g.lane)
     double lx, lv;
     M::logf_p2(A, B, pc, s, l, g, x, v, lx, lv);
     const double ua = G == 32 ? upre : mmb_uniform(&ru, 0u);  // predraw() for 32-lane groups

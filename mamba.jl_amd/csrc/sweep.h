@@ -88,6 +88,10 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
   constexpr bool PREDRAW = G == 32 && (KINDS & ((1u << MMB_SAMPLER_GIBBS) | (1u << MMB_SAMPLER_AMM))) != 0u;
   int pre0 = 0;
   double pre = 0.0;
+  // rats: the vector blocks' scalar constants, formed by one lane-parallel pass when a block
+  // needs one whose variance node was written since the last pass (models.h prep_pass); all
+  // stale here, so no value crosses a launch
+  typename M::PrepCache pk = M::prep_cache(lds);
   for (int step = 0; step < A.n_iters; ++step) {
     const int64_t it = A.iter0 + 1 + step;
 #ifdef MMB_PHASE_PROF
@@ -115,13 +119,13 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
         case MMB_SAMPLER_AMWG:
           if constexpr ((KINDS >> MMB_SAMPLER_AMWG) & 1u) {
             MMB_PROF_START
-            S::amwg(A, B, c, rn, ru, adapt, s, l, g);
+            S::amwg(A, B, c, rn, ru, adapt, s, l, g, pk);
             MMB_PROF_MARK(13, g.lane)
           }
           break;
         case MMB_SAMPLER_AMM:
           if constexpr ((KINDS >> MMB_SAMPLER_AMM) & 1u) S::amm(A, B, c, chain, it, b, rn, ru, adapt, s, l, g, lds,
-                                                                        G == 32 ? S::lane_value(pre, pre0 + b) : 0.0);
+                                                                        G == 32 ? S::lane_value(pre, pre0 + b) : 0.0, pk);
           break;
         case MMB_SAMPLER_SLICE:
           if constexpr ((KINDS >> MMB_SAMPLER_SLICE) & 1u) {
@@ -151,6 +155,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
         default:
           break;
       }
+      M::prep_wrote(pk, B);
     }
 #ifdef MMB_PHASE_PROF
     if ((threadIdx.x & 63) == 0) {

@@ -9,10 +9,10 @@ __device__ unsigned long long mmb_prof[32];
 void mmb_prof_dump() {
   unsigned long long h[32];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(mmb_prof), sizeof h) != hipSuccess) return;
-  const char* names[] = {"-", "amm:load m/fl/Mv", "amm:proposal", "amm:logf x2+accept", "amm:moments+Sigma",
+  const char* names[] = {"amm:prep", "amm:load m/fl/Mv", "amm:proposal", "amm:logf x2+accept", "amm:moments+Sigma",
                          "amm:pchol", "amm:store", "gibbs", "iteration", "count", "pchol:steps",
                          "pchol:carry", "pchol:writeback", "amwg", "slice", "draws"};
-  for (int i = 1; i < 16; ++i) fprintf(stderr, "MMB_PROF %-22s %llu\n", names[i], h[i]);
+  for (int i = 0; i < 16; ++i) fprintf(stderr, "MMB_PROF %-22s %llu\n", names[i], h[i]);
 }
 #endif
 
