@@ -68,7 +68,8 @@ typedef enum {
 } mmb_model_kind;
 
 /* node ids (Stochastic nodes that can appear in a sampling block) */
-enum { MMB_LINE_BETA = 0, MMB_LINE_S2 = 1 };
+enum { MMB_LINE_BETA = 0, MMB_LINE_S2 = 1,
+       MMB_LINE_Y = 2 /* the observed node: valid in the node lists of mmb_draws_logpdf and its kin only */ };
 enum {
   MMB_RATS_S2_C = 0, MMB_RATS_ALPHA = 1, MMB_RATS_MU_ALPHA = 2, MMB_RATS_S2_ALPHA = 3,
   MMB_RATS_BETA = 4, MMB_RATS_MU_BETA = 5, MMB_RATS_S2_BETA = 6
@@ -377,7 +378,33 @@ int mmb_hpd_get_tails(mmb_engine* e, double* below, int64_t nbelow, double* abov
 int mmb_hpd_set_tails(mmb_engine* e, const double* below, int64_t nbelow, const double* above, int64_t nabove);
 int mmb_hpd_gap(mmb_engine* e, int64_t m, int64_t total, double lo, double hi, double out[2], int64_t* index);
 
-/* Upload draws: the inverse of mmb_get_draws.  `draws` is nkept x p x K column-major (the
+/* Model log densities of the device-kept draws (modelstats.hip): logpdf(mc, nodekeys) and the pieces of
+ * dic(mc) (/root/reference/src/output/modelstats.jl:3-68).  `nodes` lists 1 <= nnodes <= MMB_IR_MAX_TERMS
+ * Stochastic node ids of the model (line: MMB_LINE_BETA / _S2 / _Y; node IR: indices of mmb_ir_model.nodes;
+ * a Logical or an id out of range is MMB_E_ARG).  For kept row i and local chain k,
+ *   lp[i,k] = sum over the list, in list order, of logpdf(node) with the node's parameters evaluated on
+ *   that draw's values (mapreduce(+), modelstats.jl:63: no early exit; sampled nodes untransformed),
+ * each term by the sweep kernel's own node log density (support -> -Inf, per-element constants, lane
+ * partials in element order and the group sum), so it has the bits the sampler computes for that state.
+ * Node IR: every sampled node that a requested node's parameter expressions read (getsimkeys,
+ * modelstats.jl:107-132; Logicals are inlined, so a monitored Logical is recomputed from its parents, not
+ * relisted from the chain), and a requested node that is itself sampled, must be monitored: else MMB_E_ARG,
+ * the message naming the first missing node id.  Hand-lowered rats (3 of 65 values monitored) and
+ * logistic: MMB_E_UNSUPPORTED.  Without device-kept draws: MMB_E_STATE.  All validation precedes any
+ * launch; none of these calls touches chain state, tune, iteration counter, draws, hpd tails or chain order.
+ * mmb_draws_logpdf (modelstats.jl:30-68): out[i + nkept*k], the value array of the n x 1 x K Chains.
+ * mmb_draws_deviance (modelstats.jl:7-8): per local chain k, with D = -2 lp,
+ *   out[2k] = sum_i (D[i,k] - shift), out[2k+1] = sum_i (D[i,k] - shift)^2, in row order; the n x K values
+ *   stay on the device.  Non-finite values propagate.  Additive across chains and GPUs for a common shift.
+ * mmb_logpdf_at (modelstats.jl:15-25): the same sum at one point x (pmon values in monitored-column
+ *   order, e.g. the posterior means), by the same kernel on a one-row, one-chain buffer. */
+int mmb_draws_logpdf(mmb_engine* e, int nnodes, const int32_t* nodes,
+                     double* out /* nkept x K, Chains order: out[i + nkept*k] */);
+int mmb_draws_deviance(mmb_engine* e, int nnodes, const int32_t* nodes, double shift, double* out /* K x 2 */);
+int mmb_logpdf_at(mmb_engine* e, int nnodes, const int32_t* nodes,
+                  const double* x /* pmon, one point in monitored-column order */, double* lp);
+
+/* Upload draws: the inverse of mmb_get_draws. `draws` is nkept x p x K column-major (the
  * Chains value layout, iteration fastest); it is transposed into the device draw buffer, which
  * grows by mmb_reserve_draws' rule, and becomes the engine's kept window (mmb_num_kept ==
  * nkept), so every device summary runs on it: a Chains read back from a file, or a series chosen

@@ -183,6 +183,25 @@ function hpd(e; alpha::Real=0.05)                 # p x 2: [lower, upper] per mo
   vals
 end
 
+# logpdf(mc, nodekeys) and the pieces of dic(mc) (modelstats.jl:3-68) on one engine's device-kept
+# draws: `nodes` are 0-based Stochastic node ids, their log densities added in list order
+function draws_logpdf(e, nodes::Vector{Int32})      # n x chains
+  out = zeros(Float64, Int(num_kept(e)), Int(num_chains(e)))
+  check(ccall((:mmb_draws_logpdf, libmambahip), Cint, (Ptr{Void}, Cint, Ptr{Int32}, Ptr{Float64}),
+              e, length(nodes), nodes, out), e); out
+end
+function draws_deviance(e, nodes::Vector{Int32}, shift::Real)   # 2 x chains: sums of D - shift and its square
+  out = zeros(Float64, 2, Int(num_chains(e)))
+  check(ccall((:mmb_draws_deviance, libmambahip), Cint, (Ptr{Void}, Cint, Ptr{Int32}, Cdouble, Ptr{Float64}),
+              e, length(nodes), nodes, shift, out), e); out
+end
+function logpdf_at(e, nodes::Vector{Int32}, x::Vector{Float64})
+  length(x) == Int(num_monitored(e)) || throw(ArgumentError("x must hold one value per monitored column"))
+  lp = zeros(Float64, 1)
+  check(ccall((:mmb_logpdf_at, libmambahip), Cint, (Ptr{Void}, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+              e, length(nodes), nodes, x, lp), e); lp[1]
+end
+
 # the one collective (mmb_comm_*): RCCL over xGMI inside the library
 function comm_id()
   id = zeros(UInt8, MMB_COMM_ID_BYTES)

@@ -23,6 +23,7 @@ MMB_HEIDEL_MAX_STARTS, MMB_RAFTERY_FIELDS = 16, 8
 MMB_ADAPT_ALL, MMB_ADAPT_BURNIN, MMB_ADAPT_NONE = 0, 1, 2
 MMB_SLICE_MULTIVARIATE, MMB_SLICE_UNIVARIATE = 0, 1
 MMB_LINE_BETA, MMB_LINE_S2 = 0, 1
+MMB_LINE_Y = 2  # the observed node: node lists of mmb_draws_logpdf / _deviance / mmb_logpdf_at only
 (MMB_RATS_S2_C, MMB_RATS_ALPHA, MMB_RATS_MU_ALPHA, MMB_RATS_S2_ALPHA, MMB_RATS_BETA, MMB_RATS_MU_BETA,
  MMB_RATS_S2_BETA) = range(7)
 MMB_LOGISTIC_BETA = 0
@@ -127,6 +128,9 @@ def _declare(lib):
         "mmb_hpd_get_tails": (C.c_int, [P, D, I64, D, I64]),
         "mmb_hpd_set_tails": (C.c_int, [P, D, I64, D, I64]),
         "mmb_hpd_gap": (C.c_int, [P, I64, I64, C.c_double, C.c_double, D, C.POINTER(I64)]),
+        "mmb_draws_logpdf": (C.c_int, [P, C.c_int, C.POINTER(I32), D]),
+        "mmb_draws_deviance": (C.c_int, [P, C.c_int, C.POINTER(I32), C.c_double, D]),
+        "mmb_logpdf_at": (C.c_int, [P, C.c_int, C.POINTER(I32), D, D]),
         "mmb_sync": (C.c_int, [P]),
         "mmb_kernel_time": (C.c_int, [P, D, C.POINTER(I64), C.POINTER(I64)]),
         "mmb_state_bytes": (C.c_int, [P, D]),

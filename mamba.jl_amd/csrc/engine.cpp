@@ -63,6 +63,12 @@ hipError_t mmb_launch_hpd_sort(uint64_t* keys, uint64_t* tmp, int64_t n, uint64_
 hipError_t mmb_launch_hpd_gap(const uint64_t* below, int64_t nb, const uint64_t* above, int64_t na, int64_t m,
                               double lo, double hi, double* part_d, long long* part_i, double* res, hipStream_t st);
 
+// modelstats.hip
+hipError_t mmb_launch_modelstats(int model, const SweepArgs& A, int nvalues, int stack, int64_t n, int K, int pmon,
+                                 const double* draws, int nnodes, const int32_t* nodes, const int32_t* col,
+                                 const int32_t* slot, int ncols, double* lp, hipStream_t st);
+hipError_t mmb_launch_deviance(int64_t rows, int K, const double* lp, double shift, double* acc, hipStream_t st);
+
 hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
 
 static thread_local std::string g_last_error;
@@ -2305,6 +2311,167 @@ int mmb_hpd_gap(mmb_engine* e, int64_t m, int64_t total, double lo, double hi, d
   memcpy(out, h, 2 * sizeof(double));
   *index = (int64_t)h[2];
   return 0;
+}
+
+// ---------------------------------------------------------------- model statistics (modelstats.jl)
+// The plan of a node list: validated ids and, for node-IR models, the monitored columns to load and the
+// state slots they fill.  getsimkeys (modelstats.jl:107-132) relists the sampled nodes the requested nodes
+// depend on through Logicals; here that is the read set of their parameter expressions (Logicals are
+// inlined): the VAL / VALI / VALG words over every element, VALG through the gather indices in the pool.
+struct MsPlan {
+  std::vector<int32_t> col, slot;
+};
+
+static int ms_plan(mmb_engine* e, int nnodes, const int32_t* nodes, bool need_draws, MsPlan& pl) {
+  if (e->model == MMB_MODEL_RATS)
+    return fail(e, MMB_E_UNSUPPORTED, "logpdf: the hand-lowered rats model monitors 3 of its 65 values (s2_c, mu_beta, "
+                "alpha0): alpha and beta are not in the chains, so the nodes cannot be relisted from the draws "
+                "(use the node-IR rats model with alpha, beta and the hyper-parameters monitored)");
+  if (e->model == MMB_MODEL_LOGISTIC)
+    return fail(e, MMB_E_UNSUPPORTED, "logpdf: the logistic model evaluates its likelihood through its own batched "
+                "engine; its model statistics are not lowered yet");
+  if (!e->d_vals || (need_draws && e->n_kept < 1))
+    return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
+  if (nnodes < 1 || nnodes > MMB_IR_MAX_TERMS) return fail(e, MMB_E_ARG, "1 <= nnodes <= %d", MMB_IR_MAX_TERMS);
+  if (e->model == MMB_MODEL_LINE) {
+    for (int a = 0; a < nnodes; ++a)
+      if (nodes[a] < 0 || nodes[a] > MMB_LINE_Y)
+        return fail(e, MMB_E_ARG, "node id %d is not a Stochastic node of the line model", nodes[a]);
+    return 0;
+  }
+  const int NN = (int)e->ir_nodes.size();
+  std::vector<int> colstart(NN, -1);  // first monitored column of a node, -1: not monitored
+  int c0 = 0;
+  for (int32_t nid : e->ir_mon) {
+    colstart[nid] = c0;
+    c0 += e->ir_nodes[nid].len;
+  }
+  auto sampled = [&](const mmb_ir_node& N) { return !N.fixed && N.family != MMB_IR_LOGICAL; };
+  std::vector<char> need(NN, 0);
+  for (int a = 0; a < nnodes; ++a) {
+    const int nid = nodes[a];
+    if (nid < 0 || nid >= NN || e->ir_nodes[nid].family == MMB_IR_LOGICAL)
+      return fail(e, MMB_E_ARG, "node id %d is not a Stochastic node of the model", nid);
+    const mmb_ir_node& N = e->ir_nodes[nid];
+    if (sampled(N)) need[nid] = 1;
+    std::vector<int> slots;
+    for (int k = 0; k < 3; ++k) {
+      if (N.expr[k] < 0) continue;
+      const int ne = (N.family == MMB_IR_ISONORMAL && k == 1) ? 1 : N.len;
+      for (int i = 0; i < ne; ++i) ir_expr_slots(e->ir_code, e->ir_pool, N.expr[k], i, slots);
+    }
+    for (int s : slots) {
+      int owner = -1;
+      for (int q = 0; q < NN; ++q) {
+        const mmb_ir_node& Q = e->ir_nodes[q];
+        if (sampled(Q) && s >= Q.off && s < Q.off + Q.len) owner = q;
+      }
+      if (owner < 0) return fail(e, MMB_E_ARG, "node id %d reads value slot %d, which no sampled node owns", nid, s);
+      need[owner] = 1;
+    }
+  }
+  for (int q = 0; q < NN; ++q)
+    if (need[q] && colstart[q] < 0)
+      return fail(e, MMB_E_ARG, "node id %d is not monitored: the requested nodes need its draws", q);
+  for (int q = 0; q < NN; ++q) {
+    if (!need[q]) continue;
+    const mmb_ir_node& Q = e->ir_nodes[q];
+    for (int i = 0; i < Q.len; ++i) {
+      pl.col.push_back(colstart[q] + i);
+      pl.slot.push_back(Q.off + i);
+    }
+  }
+  return 0;
+}
+
+// lp of the n x K rows of `draws` into d_lp ([n][K], device), rows [r0, r0 + rows)
+static hipError_t ms_launch(mmb_engine* e, const SweepArgs& A, const MsPlan& pl, const int32_t* d_col,
+                            const int32_t* d_slot, int64_t rows, int K, const double* draws, int nnodes,
+                            const int32_t* nodes, double* d_lp) {
+  return mmb_launch_modelstats(e->model, A, e->P, e->ir_stack, rows, K, e->pmon, draws, nnodes, nodes, d_col, d_slot,
+                               (int)pl.col.size(), d_lp, e->stream);
+}
+
+// rows of the device lp scratch per pass: the n x K values are formed (and, for the deviance, reduced) in
+// chunks of at most this many doubles
+constexpr int64_t MS_CHUNK = 8ll << 20;
+
+// shared body: out_lp (host, Chains order out[i + n*k]) and / or acc (host, K x 2 deviance sums with `shift`)
+static int ms_run(mmb_engine* e, const char* what, int nnodes, const int32_t* nodes, int64_t n, int K,
+                  const double* draws, double* out_lp, double shift, double* acc) {
+  MsPlan pl;
+  if (int rc = ms_plan(e, nnodes, nodes, true, pl)) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  SweepArgs A;
+  fill_args(e, A);
+  const int64_t crows = std::max<int64_t>(1, std::min<int64_t>(n, MS_CHUNK / K));
+  int32_t* d_tab = nullptr;
+  double *d_lp = nullptr, *d_acc = nullptr;
+  const size_t nc = pl.col.size();
+  hipError_t st = hipSuccess;
+  if (nc) {
+    st = hipMalloc(&d_tab, 2 * nc * sizeof(int32_t));
+    if (st == hipSuccess)
+      st = hipMemcpyAsync(d_tab, pl.col.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess)
+      st = hipMemcpyAsync(d_tab + nc, pl.slot.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+  }
+  if (st == hipSuccess) st = hipMalloc(&d_lp, (size_t)crows * K * sizeof(double));
+  if (st == hipSuccess && acc) {
+    st = hipMalloc(&d_acc, (size_t)2 * K * sizeof(double));
+    if (st == hipSuccess) st = hipMemsetAsync(d_acc, 0, (size_t)2 * K * sizeof(double), e->stream);
+  }
+  std::vector<double> h;
+  if (out_lp) h.resize((size_t)crows * K);
+  for (int64_t r0 = 0; r0 < n && st == hipSuccess; r0 += crows) {
+    const int64_t rows = std::min(crows, n - r0);
+    st = ms_launch(e, A, pl, d_tab, d_tab ? d_tab + nc : nullptr, rows, K,
+                   draws + (size_t)r0 * e->pmon * K, nnodes, nodes, d_lp);
+    if (st == hipSuccess && acc) st = mmb_launch_deviance(rows, K, d_lp, shift, d_acc, e->stream);
+    if (st == hipSuccess && out_lp) {
+      st = hipMemcpyAsync(h.data(), d_lp, (size_t)rows * K * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+      if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+      if (st == hipSuccess)
+        for (int64_t i = 0; i < rows; ++i)
+          for (int64_t k = 0; k < K; ++k) out_lp[(r0 + i) + n * k] = h[(size_t)i * K + k];
+    }
+  }
+  if (st == hipSuccess && acc)
+    st = hipMemcpyAsync(acc, d_acc, (size_t)2 * K * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+  if (d_tab) (void)hipFree(d_tab);
+  if (d_lp) (void)hipFree(d_lp);
+  if (d_acc) (void)hipFree(d_acc);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "%s: %s", what, hipGetErrorString(st));
+  return 0;
+}
+
+int mmb_draws_logpdf(mmb_engine* e, int nnodes, const int32_t* nodes, double* out) {
+  if (!e || !nodes || !out) return fail(e, MMB_E_ARG, "null argument");
+  return ms_run(e, "draws_logpdf", nnodes, nodes, e->n_kept, (int)e->K, e->d_draws, out, 0.0, nullptr);
+}
+
+int mmb_draws_deviance(mmb_engine* e, int nnodes, const int32_t* nodes, double shift, double* out) {
+  if (!e || !nodes || !out) return fail(e, MMB_E_ARG, "null argument");
+  return ms_run(e, "draws_deviance", nnodes, nodes, e->n_kept, (int)e->K, e->d_draws, nullptr, shift, out);
+}
+
+int mmb_logpdf_at(mmb_engine* e, int nnodes, const int32_t* nodes, const double* x, double* lp) {
+  if (!e || !nodes || !x || !lp) return fail(e, MMB_E_ARG, "null argument");
+  {  // validated before anything is allocated (ms_run validates again on the same arguments)
+    MsPlan pl;
+    if (int rc = ms_plan(e, nnodes, nodes, true, pl)) return rc;
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  double* d_x = nullptr;  // a one-row, one-chain draw buffer
+  HIPCHK(e, hipMalloc(&d_x, (size_t)e->pmon * sizeof(double)));
+  hipError_t st = hipMemcpyAsync(d_x, x, (size_t)e->pmon * sizeof(double), hipMemcpyHostToDevice, e->stream);
+  int rc = 0;
+  if (st != hipSuccess) rc = fail(e, MMB_E_HIP, "logpdf_at: %s", hipGetErrorString(st));
+  else rc = ms_run(e, "logpdf_at", nnodes, nodes, 1, 1, d_x, lp, 0.0, nullptr);
+  (void)hipStreamSynchronize(e->stream);
+  (void)hipFree(d_x);
+  return rc;
 }
 
 // ---------------------------------------------------------------- per-chain diagnostics

@@ -353,6 +353,11 @@ class Model(_BaseModel):
             raise ArgumentError("node-IR model: call init_matrix (setinits!) first")
         return super().spec()
 
+    def stats_table(self):
+        if not self.compiled:
+            raise ArgumentError("node-IR model: call init_matrix (setinits!) first")
+        return self._stats
+
     def ir(self):
         if not self.compiled:
             raise ArgumentError("node-IR model: call init_matrix (setinits!) first")
@@ -367,6 +372,7 @@ class _Lowering:
         self.code, self.consts, self.pool = [], [], []
         self.pool_of = {}
         self.depth = 1
+        self.fixed_reads = set()  # fixed (observed) Stochastic nodes some node's expressions read
 
     # -- pool / const helpers
     def const(self, v):
@@ -474,6 +480,8 @@ class _Lowering:
                 refs.add(e.name)
                 return push(self.word(op["val"], (m.nodes[e.name].offset + e.k - 1)))
             if k in ("fixed", "data"):
+                if k == "fixed":
+                    self.fixed_reads.add(e.name)
                 v = m.fixed_vals[e.name] if k == "fixed" else m.inputs[e.name]
                 return push(self.word(op["datas"], self.put(("elem", e.name, e.k), v[e.k - 1:e.k])))
             raise ArgumentError("element of a logical: index its parents instead")
@@ -491,6 +499,8 @@ class _Lowering:
                 refs.add(e.name)
                 o = m.nodes[e.name].offset
                 return push(self.word(op["val"] if ln == 1 else op["vali"], o))
+            if k == "fixed":
+                self.fixed_reads.add(e.name)
             v = m.fixed_vals[e.name] if k == "fixed" else m.inputs[e.name]
             o = self.put(("v", e.name), v)
             return push(self.word(op["datas"] if ln == 1 else op["data"], o))
@@ -511,6 +521,8 @@ class _Lowering:
                 self.code.append(w)
                 return sp2
             if k in ("fixed", "data"):
+                if k == "fixed":
+                    self.fixed_reads.add(e.name)
                 v = m.fixed_vals[e.name] if k == "fixed" else m.inputs[e.name]
                 return push(self.word(op["data"], self.put(("g", e.name, e.idx), v[(idx - 1).astype(int)])))
             raise ArgumentError("gather from a logical: gather its parents instead")
@@ -638,6 +650,7 @@ class _Lowering:
                 elif np.any((x != 0) & (x != 1)):
                     raise ArgumentError(f"{n}: Bernoulli observations must be 0/1")
             parents[n] = refs
+        node_fixed_reads = set(self.fixed_reads)  # (the Gibbs closures below read observed nodes too)
         # targets (stochastic children through logicals) and topological order
         children = {n: [c for c in m.stoch if n in parents[c]] for n in m.stoch}
         indeg = {n: builtins.sum(1 for p in parents[n] if p != n) for n in m.stoch}
@@ -678,6 +691,12 @@ class _Lowering:
             raise ArgumentError("node expression too deep")
         m.monitor_names = names
         m.topo = topo
+        # the node table of the model statistics (Model.keys, modelstats.py): an output node is an
+        # observed Stochastic node that no other node reads
+        m.parents = parents
+        m._stats = {"stoch": list(m.stoch), "output": [n for n in m.fixed if n not in node_fixed_reads],
+                    "parents": parents, "sampled": set(m.params),
+                    "monitored": {n for n in m.params if m.defs[n].monitor}, "ids": {n: ids[n] for n in m.stoch}}
         keep = {"nodes": nodes, "code": np.asarray(self.code, dtype=np.int32),
                 "consts": np.asarray(self.consts + [0.0], dtype=np.float64),
                 "pool": np.asarray(self.pool + [0.0], dtype=np.float64),

@@ -247,6 +247,38 @@ class Engine:
         self._chk(self.lib.mmb_hpd_gap(self.h, int(m), int(total), float(lo), float(hi), abi.dptr(out), C.byref(idx)))
         return out, int(idx.value)
 
+    # model log densities of the device-kept draws (modelstats.py maps names and closes dic)
+    def _node_list(self, nodes):
+        ids = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        return ids, ids.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def draws_logpdf(self, nodes):
+        """n x K: the sum of the listed nodes' log densities at every kept draw (mmb_draws_logpdf,
+        modelstats.jl:30-68); `nodes` are engine node ids, summed in list order."""
+        ids, p = self._node_list(nodes)
+        out = np.empty((max(self.num_kept(), 0), self.K), order="F")
+        self._chk(self.lib.mmb_draws_logpdf(self.h, int(ids.size), p, abi.dptr(out)))
+        return out
+
+    def draws_deviance(self, nodes, shift):
+        """K x 2: per chain [sum_i (D - shift), sum_i (D - shift)^2] of D = -2 logpdf over the kept
+        draws, in row order (mmb_draws_deviance); the n x K values stay on the device."""
+        ids, p = self._node_list(nodes)
+        out = np.empty((self.K, 2))
+        self._chk(self.lib.mmb_draws_deviance(self.h, int(ids.size), p, float(shift), abi.dptr(out)))
+        return out
+
+    def logpdf_at(self, nodes, x):
+        """The listed nodes' log density at one point `x` (pmon values in monitored-column order),
+        by the kernel of draws_logpdf on a one-row buffer (mmb_logpdf_at, modelstats.jl:15-25)."""
+        ids, p = self._node_list(nodes)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.pmon:
+            raise ArgumentError(f"the point must have {self.pmon} values, got {x.size}")
+        lp = C.c_double()
+        self._chk(self.lib.mmb_logpdf_at(self.h, int(ids.size), p, abi.dptr(x), C.byref(lp)))
+        return lp.value
+
     def set_draws(self, value):
         """Upload `value` (n x p x chains, the Chains layout) as the device-kept draws
         (mmb_set_draws, the inverse of `draws`): the device summaries then run on it."""
@@ -427,6 +459,19 @@ class Chains:
         """cor(c) (stats.jl:15-17): the p x p correlation matrix of the draws pooled over chains."""
         from .gelman import cor_sharded
         return cor_sharded(self._device_engine())
+
+    def logpdf(self, nodekeys=None):
+        """logpdf(mc[, nodekeys]) (modelstats.jl:28-51): the summed log density of the listed
+        Stochastic nodes (default: all) at every kept draw, a Chains n x 1 x chains named
+        ["logpdf"].  Every sampled node the list needs must be monitored."""
+        from .modelstats import logpdf
+        return logpdf(self, nodekeys)
+
+    def dic(self):
+        """dic(mc) (modelstats.jl:3-12): (2 x 2 [DIC, Effective Parameters] for pD and pV, row
+        labels, column labels), from the deviance of the output nodes on the device-kept draws."""
+        from .modelstats import dic
+        return dic(self)
 
 
 def mcmc(model, inputs, inits, iters, burnin=0, thin=1, chains=1, verbose=False, device=0,

@@ -40,6 +40,7 @@ class Model:
         self.iter = 0
         self.burnin = 0
         self._keep = []
+        self._stats = None
 
     # ---- setsamplers! (initialization.jl:42-48) ----
     def setsamplers(self, samplers):
@@ -120,6 +121,26 @@ class Model:
         self._keep = keep
         return sp
 
+    # ---- keys(m, ntype) (model.jl:58-72, 153-163, 175-183) and the tables of modelstats.py ----
+    def stats_table(self):
+        """The model's Stochastic nodes as the model statistics see them (modelstats.py): `stoch`
+        names in declaration order, `output` the observed ones no node reads, `parents[name]` the
+        sampled nodes its distribution parameters read (through Logicals), `sampled` the nodes some
+        block updates, `monitored` those of them whose draws are in the chains, `ids[name]` the engine's node id."""
+        if self._stats is None:
+            raise ArgumentError("this model has no node table for model statistics")
+        return self._stats
+
+    def keys(self, kind="stochastic"):
+        """keys(m, :stochastic) / keys(m, :output): an output node is an observed Stochastic
+        node that no other node reads."""
+        t = self.stats_table()
+        if kind == "stochastic":
+            return list(t["stoch"])
+        if kind == "output":
+            return list(t["output"])
+        raise ArgumentError(f"unsupported node type {kind}: stochastic or output")
+
     def data_arrays(self):
         """Inputs in the order the oracle/engine expect (tests use this for the oracle)."""
         if self.inputs is None:
@@ -130,7 +151,11 @@ class Model:
 def line():
     """doc/tutorial/line.jl:5-25"""
     nodes = [Node("beta", abi.MMB_LINE_BETA, 0, 2, False), Node("s2", abi.MMB_LINE_S2, 2, 1, True)]
-    return Model(abi.MMB_MODEL_LINE, nodes, 3, ["beta[1]", "beta[2]", "s2"], ["x", "y"])
+    m = Model(abi.MMB_MODEL_LINE, nodes, 3, ["beta[1]", "beta[2]", "s2"], ["x", "y"])
+    m._stats = {"stoch": ["y", "beta", "s2"], "output": ["y"],
+                "parents": {"y": {"beta", "s2"}, "beta": set(), "s2": set()}, "sampled": {"beta", "s2"},
+                "monitored": {"beta", "s2"}, "ids": {"beta": abi.MMB_LINE_BETA, "s2": abi.MMB_LINE_S2, "y": abi.MMB_LINE_Y}}
+    return m
 
 
 def rats():
@@ -140,13 +165,23 @@ def rats():
              Node("s2_alpha", abi.MMB_RATS_S2_ALPHA, 32, 1, True),
              Node("beta", abi.MMB_RATS_BETA, 33, 30, False), Node("mu_beta", abi.MMB_RATS_MU_BETA, 63, 1, False),
              Node("s2_beta", abi.MMB_RATS_S2_BETA, 64, 1, True)]
-    return Model(abi.MMB_MODEL_RATS, nodes, 65, ["s2_c", "mu_beta", "alpha0"], ["y", "x"])
+    m = Model(abi.MMB_MODEL_RATS, nodes, 65, ["s2_c", "mu_beta", "alpha0"], ["y", "x"])
+    names = [n.name for n in nodes]
+    m._stats = {"stoch": ["y"] + names, "output": ["y"],
+                "parents": {"y": {"alpha", "beta", "s2_c"}, "alpha": {"mu_alpha", "s2_alpha"},
+                            "beta": {"mu_beta", "s2_beta"}, **{k: set() for k in names if k not in ("alpha", "beta")}},
+                "sampled": set(names), "monitored": {"s2_c", "mu_beta"},  # alpha0 is a Logical
+                "ids": {**{n.name: n.id for n in nodes}, "y": len(nodes)}}
+    return m
 
 
 def logistic(nobs, ncoef, prior_sd=10.0):
     nodes = [Node("beta", abi.MMB_LOGISTIC_BETA, 0, ncoef, False)]
-    return Model(abi.MMB_MODEL_LOGISTIC, nodes, ncoef, [f"beta[{i + 1}]" for i in range(ncoef)],
-                 ["X", "y"], nobs=nobs, ncoef=ncoef, prior_sd=prior_sd)
+    m = Model(abi.MMB_MODEL_LOGISTIC, nodes, ncoef, [f"beta[{i + 1}]" for i in range(ncoef)],
+              ["X", "y"], nobs=nobs, ncoef=ncoef, prior_sd=prior_sd)
+    m._stats = {"stoch": ["y", "beta"], "output": ["y"], "parents": {"y": {"beta"}, "beta": set()},
+                "sampled": {"beta"}, "monitored": {"beta"}, "ids": {"beta": abi.MMB_LOGISTIC_BETA, "y": 1}}
+    return m
 
 
 # ---- reference data / inits ------------------------------------------------------
