@@ -91,9 +91,13 @@ struct DBlock {
   double* t_sigma;       // AMWG  [K][DP]
   double* t_accept;      // AMWG  [K][DP]
   int32_t* t_m;          // AMWG/AMM/NUTS m [K]
-  int32_t* t_flags;      // [K] bit0 adapt, bit1 AMM alias, bit2 AMM factor valid, bit3 NUTS init
+  int32_t* t_flags;      // [K] bit0 adapt, bit1 AMM alias, bit2 AMM factor valid, bit3 NUTS init,
+                         //     bit4 AMM factor not stored yet (samplers.h amm: set and cleared within a launch)
   double* t_Mv;          // AMM   [K][DP]
   double* t_Mvv;         // AMM   [K][TP] packed lower, row-major (slot(i,k) = i(i+1)/2 + k)
+  double* t_Mv_alt;      // AMM   second copy of t_Mv / t_Mvv or null.  Non-null: the moments after m adaptive
+  double* t_Mvv_alt;     //       updates are in the copy of m's parity (odd: _alt), so those of m - 1 outlive
+                         //       update m (samplers.h amm: lazy factor store); null: one copy, updated in place
   double* t_Ls;          // AMM   [K][TP] factor, in-place slot storage
   uint8_t* t_piv;        // AMM   [K][DP] pivot order
   double* t_xnext;       // AMM   [K][DP] next iteration's proposal minus v (samplers.h amm: formed

@@ -85,6 +85,9 @@ struct BlockHost {
   bool sigl_diag = false;
   // device
   double *sigma = nullptr, *accept = nullptr, *Mv = nullptr, *Mvv = nullptr, *Ls = nullptr;
+  // AMM second moment buffers (32-lane kernels that carry proposals; DBlock::t_Mv_alt): chain k's
+  // current Mv / Mvv are in these when its m is odd.  Null: one buffer
+  double *Mv_alt = nullptr, *Mvv_alt = nullptr;
   double *nuts = nullptr, *nfr = nullptr, *width = nullptr, *sigl_d = nullptr;
   double* hmc = nullptr;  // HMC/MALA [K][2] epsilon, L
   int32_t *m = nullptr, *flags = nullptr;
@@ -854,7 +857,7 @@ int mmb_ir_jit_info(const mmb_engine* e, char* buf, int64_t n) {
 static void free_dev(mmb_engine* e) {
   for (auto& h : e->blocks) {
     void* ptrs[] = {h.sigma, h.accept, h.Mv, h.Mvv, h.Ls, h.nuts, h.nfr, h.width, h.sigl_d, h.hmc, h.m, h.flags,
-                    h.piv, h.xnext, h.xtag, h.astat};
+                    h.piv, h.xnext, h.xtag, h.astat, h.Mv_alt, h.Mvv_alt};
     for (void* p : ptrs)
       if (p) (void)hipFree(p);
     h.sigma = h.accept = h.Mv = h.Mvv = h.Ls = h.nuts = h.nfr = h.width = h.sigl_d = h.hmc = nullptr;
@@ -863,6 +866,7 @@ static void free_dev(mmb_engine* e) {
     h.xnext = nullptr;
     h.xtag = nullptr;
     h.astat = nullptr;
+    h.Mv_alt = h.Mvv_alt = nullptr;
   }
   if (e->d_vals) (void)hipFree(e->d_vals);
   if (e->d_blocks) (void)hipFree(e->d_blocks);
@@ -1123,7 +1127,7 @@ static int upload_blocks(mmb_engine* e) {
     d.width = (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) ? h.width : nullptr;
     d.sigl = h.sigl_d;
     d.t_sigma = h.sigma; d.t_accept = h.accept; d.t_m = h.m; d.t_flags = h.flags;
-    d.t_Mv = h.Mv; d.t_Mvv = h.Mvv; d.t_Ls = h.Ls; d.t_piv = h.piv; d.t_xnext = h.xnext; d.t_xtag = h.xtag; d.t_nuts = h.nuts; d.t_nfr = h.nfr;
+    d.t_Mv = h.Mv; d.t_Mvv = h.Mvv; d.t_Mv_alt = h.Mv_alt; d.t_Mvv_alt = h.Mvv_alt; d.t_Ls = h.Ls; d.t_piv = h.piv; d.t_xnext = h.xnext; d.t_xtag = h.xtag; d.t_nuts = h.nuts; d.t_nfr = h.nfr;
     d.t_astat = h.astat;
     d.t_hmc = h.hmc;
     d.ir_blk = (int32_t)b;
@@ -1147,6 +1151,8 @@ static int upload_blocks(mmb_engine* e) {
   HIPCHK(e, hipMemcpy(e->d_blocks, db.data(), db.size() * sizeof(DBlock), hipMemcpyHostToDevice));
   return 0;
 }
+
+static bool amm_posform(const mmb_engine* e);
 
 template <class T>
 static hipError_t dalloc(T** p, size_t n) {
@@ -1193,6 +1199,12 @@ int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_
       HIPCHK(e, hipMemset(h.Mv, 0, K * DP * sizeof(double)));
       HIPCHK(e, hipMemset(h.Mvv, 0, K * TP * sizeof(double)));
       HIPCHK(e, hipMemset(h.Ls, 0, K * TP * sizeof(double)));
+      if (amm_posform(e)) {  // the kernels of samplers.h amm's lazy factor store
+        HIPCHK(e, dalloc(&h.Mv_alt, K * DP));
+        HIPCHK(e, dalloc(&h.Mvv_alt, K * TP));
+        HIPCHK(e, hipMemset(h.Mv_alt, 0, K * DP * sizeof(double)));
+        HIPCHK(e, hipMemset(h.Mvv_alt, 0, K * TP * sizeof(double)));
+      }
       std::vector<uint8_t> pv(K * DP);
       for (int64_t k = 0; k < K; ++k)
         for (size_t i = 0; i < DP; ++i) pv[k * DP + i] = (uint8_t)i;
@@ -1928,6 +1940,15 @@ int mmb_get_tune(mmb_engine* e, double* tune) {
       if ((rc = d2h(e, mv, h.Mv, K * DP)) || (rc = d2h(e, mvv, h.Mvv, K * TP)) ||
           (rc = d2h(e, ls, h.Ls, K * TP)) || (rc = d2h(e, pv, h.piv, K * DP)))
         return rc;
+      if (h.Mv_alt) {  // two moment buffers: chain k's current ones are those of m[k]'s parity
+        std::vector<double> mva, mvva;
+        if ((rc = d2h(e, mva, h.Mv_alt, K * DP)) || (rc = d2h(e, mvva, h.Mvv_alt, K * TP))) return rc;
+        for (int64_t k = 0; k < K; ++k) {
+          if (!(m[k] & 1)) continue;
+          std::copy(&mva[k * DP], &mva[k * DP] + DP, &mv[k * DP]);
+          std::copy(&mvva[k * TP], &mvva[k * TP] + TP, &mvv[k * TP]);
+        }
+      }
       for (int64_t k = 0; k < K; ++k) {
         double* t = tune + k * TL + off;
         t[0] = (fl[k] & 1) ? 1.0 : 0.0;
@@ -2040,6 +2061,8 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
       if ((rc = h2d(e, h.Mv, mv)) || (rc = h2d(e, h.Mvv, mvv)) || (rc = h2d(e, h.Ls, ls)) ||
           (rc = h2d(e, h.piv, pv)))
         return rc;
+      // two moment buffers: both get the row, so the one of the chain's m holds it
+      if (h.Mv_alt && ((rc = h2d(e, h.Mv_alt, mv)) || (rc = h2d(e, h.Mvv_alt, mvv)))) return rc;
     } else if (h.spec.sampler == MMB_SAMPLER_NUTS) {
       std::vector<double> nt(K * 8, 0.0);
       for (int64_t k = 0; k < K; ++k) {

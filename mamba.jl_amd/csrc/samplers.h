@@ -406,23 +406,24 @@ struct Smp {
   // On full rank the factor is left in `mat` in POSITION form (row at pivot position t, i.e.
   // row piv[t] of P'L... stored at tri(t) .. tri(t) + t, step order), and *pos receives this
   // lane's position; amm() stores it with the position bytes (the host converts to the
-  // canonical slot form + pivot order, engine.cpp).
+  // canonical slot form + pivot order, engine.cpp).  wb = false skips that write-back.
   __device__ __forceinline__ static int pchol32(int d, double* mat, double* prow, int* pks, const Grp<G>& g,
                                                 int* pos_out, const DBlock* NB = nullptr,
                                                 const SweepArgs& A = SweepArgs{}, int c = 0, uint32_t chain = 0,
-                                                int64_t it = 0, int b = 0, int m = 0, int* redo = nullptr) {
+                                                int64_t it = 0, int b = 0, int m = 0, int* redo = nullptr,
+                                                bool wb = true) {
     // a block as wide as the model's DMAX (rats: both 30-d blocks) runs a copy with d a
     // compile-time constant: no per-step scalar test and branch of j against d (9.58e7 ->
     // 9.90e7 rats chain-updates/s, A/B on one box, parity unchanged)
     if (d == DMAX)
-      return pchol32_impl<true>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo);
-    return pchol32_impl<false>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo);
+      return pchol32_impl<true>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo, wb);
+    return pchol32_impl<false>(d, mat, prow, pks, pos_out, NB, A.seed, A.xepoch, c, chain, it, b, m, redo, wb);
   }
   template <bool FULLD>
   __device__ __forceinline__ static int pchol32_impl(int d_arg, double* mat, double* prow, int* pks, int* pos_out,
                                                      const DBlock* NB, uint64_t seed, int64_t xepoch, int c,
                                                      uint32_t chain, int64_t it, int b, int m,
-                                                     int* redo_out) {
+                                                     int* redo_out, bool wb) {
     const int d = FULLD ? DMAX : d_arg;
     const Grp<G> g;
     constexpr int RI = DMAX;  // prow[RI]: the pivot's reciprocal
@@ -467,7 +468,9 @@ struct Smp {
         if (lane == 0) NB->t_xtag[c] = (xepoch << 32) | (int64_t)(uint32_t)(it + 1);  // xtag()
       }
       MMB_PROF_MARK(11, lane)
-      if (rank == d && inb) {  // the factor in position form: row at position pe at tri(pe) + k
+      // (wb, wave-uniform: false when the caller will not read the factor from `mat`, amm()'s
+      // lazy factor store; `mat` then still holds Sigma)
+      if (wb && rank == d && inb) {  // the factor in position form: row at position pe at tri(pe) + k
         // one store per k from every lane, no exec-mask change: entries past the row's end
         // (k > pe, exact zeros) go to the lane's own dummy slot in the idle pivot-row buffer
         const int base = mmb_tri(pe);
@@ -739,7 +742,7 @@ struct Smp {
   __device__ __forceinline__ static void amm(const SweepArgs& A, const DBlock& B, int c, uint32_t chain,
                              int64_t it, int b, const mmb_rng& rn,
                              const mmb_rng& ru, bool adapt, St& s, const Lc& l, const Grp<G>& g,
-                             double* lds, double upre, typename M::PrepCache& pk) {
+                             double* lds, double upre, typename M::PrepCache& pk, bool& rec) {
     const int d = B.d;
     const int T = mmb_tri(d);
     double* mat = lds;
@@ -747,15 +750,68 @@ struct Smp {
     double* vvs = z2s + DP;
     double* mvs = vvs + DP;
     int* ia = (int*)(mvs + DP);  // piv / pos scratch (2*DP ints)
-    double v[R], x[R], z1[R], z2[R], mv[R];
     MMB_PROF_START
+    int m, fl;
+    int* pks = (int*)z2s;  // pivot order (group-uniform values), LDS
+    const bool carry = CARRY && B.t_xtag != nullptr && B.sigl_diag;
+    bool lazy = false;
+    // Lazy factor store (carried proposals, two moment buffers).  Within a launch nothing reads
+    // t_Ls / t_piv of a chain whose update was full rank: the next proposal is the carry and the
+    // next full-rank update overwrites them.  So a full-rank update whose successor runs in this
+    // launch and adapts (both wave-uniform, known before the factorization) keeps its factor in
+    // registers only -- no LDS write-back, no store -- and marks the chain (flag bit 4, STALE).
+    // The one reader left is a marked chain whose NEXT update is rank deficient (amm.jl:88-90
+    // keeps the older SigmaLm; a rounding event).  That update returns rec = true and the sweep
+    // runs the block again at once (sweep.h: the block loop re-enters this one copy of the code):
+    // the second visit (`recover`) does nothing but rebuild Sigma of the update before from the
+    // other moment buffer, by the operations of the moment update's Sigma line, factorize it
+    // again (the same bits) and store that factor; no proposal, no carry, no counters.  A wave
+    // partner that does not recover rides along on whatever its `mat` holds and stores nothing.
+    // The launch's last iteration always stores, so no mark crosses a launch.
+    constexpr int STALE = 16;
+    if constexpr (CARRY)
+      lazy = carry && B.t_Mv_alt != nullptr && it != A.iter0 + A.n_iters &&
+             (B.adapt == MMB_ADAPT_ALL || (B.adapt == MMB_ADAPT_BURNIN && it + 1 <= A.model_burnin));
+    bool recover = false;  // wave-uniform
+    if constexpr (CARRY) recover = __ballot(rec) != 0;
+    if (__builtin_expect(recover, 0)) {
+      // Sigma(m - 1) = cc (Mvv - Mv Mv') from the buffer of the other parity, p and cc of m - 1
+      // (a marked chain's previous update was full rank, so it was not the fresh one)
+      m = B.t_m[c];
+      fl = B.t_flags[c];
+      const int mp = m - 1;
+      const double pp = (double)mp / ((double)mp + 1.0);
+      const double ccp = (B.scale * B.scale / (double)d) / pp;
+      const double* MvvP = ((mp & 1) ? B.t_Mvv_alt : B.t_Mvv) + (size_t)c * TP;
+      const double* MvP = ((mp & 1) ? B.t_Mv_alt : B.t_Mv) + (size_t)c * DP;
+      double* mvp = (double*)ia;  // the pivot-row buffer, idle between factorizations
+      if (rec && g.lane < d) mvp[g.lane] = MvP[g.lane];
+      grp_sync();
+      if (rec) {
+        for (int t = g.lane; t < TP; t += G) {
+          int i, k;
+          slot_ik(t, i, k);
+          mat[t] = ccp * (MvvP[t] - mvp[k] * mvp[i]);
+        }
+      }
+      M::stash(lds, s, g.lane);
+      grp_sync();
+    } else {
+    double v[R], x[R], z1[R], z2[R], mv[R];
     M::unlist(B, s, g.lane, v);
-    int m = B.t_m[c];
-    int fl = B.t_flags[c];
+    m = B.t_m[c];
+    fl = B.t_flags[c];
+    // two moment buffers (DBlock::t_Mv_alt): the current Mv is in the copy of m's parity; both
+    // loads are issued with the load of m (no address that waits for it)
+    const bool dual = CARRY && B.t_Mv_alt != nullptr;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       int e = r * G + g.lane;
       mv[r] = e < d ? B.t_Mv[(size_t)c * DP + e] : 0.0;
+      if constexpr (CARRY) {
+        const double alt = (dual && e < d) ? B.t_Mv_alt[(size_t)c * DP + e] : 0.0;
+        mv[r] = (dual && (m & 1)) ? alt : mv[r];
+      }
     }
     const bool fresh = adapt && !(fl & 1);
     bool carried = false;
@@ -880,7 +936,18 @@ struct Smp {
       for (int r = 0; r < R; ++r) v[r] = x[r];
     }
     MMB_PROF_MARK(3, g.lane)
-    if (adapt) {  // amm.jl:81-91
+    if (!adapt) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        int e = r * G + g.lane;
+        if (e < d) ((dual && (m & 1)) ? B.t_Mv_alt : B.t_Mv)[(size_t)c * DP + e] = mv[r];
+      }
+      if (g.lane == 0) { B.t_m[c] = m; B.t_flags[c] = fl; }
+      grp_sync();
+      M::relist(B, s, g, v);
+      return;
+    }
+    {  // amm.jl:81-91
       m += 1;
       const double p = (double)m / ((double)m + 1.0);
       const double q = 1.0 - p;
@@ -901,7 +968,9 @@ struct Smp {
         if (e < d) vm[e] = make_double2(v[r], mv[r]);
       }
       const double cc = (B.scale * B.scale / (double)d) / p;
-      double* Mvv = B.t_Mvv + (size_t)c * TP;
+      // two moment buffers: read Mvv(m - 1) from the copy of that parity, write Mvv(m) to the other
+      double* Mvv = ((dual && ((m - 1) & 1)) ? B.t_Mvv_alt : B.t_Mvv) + (size_t)c * TP;
+      double* Mvv_w = ((dual && (m & 1)) ? B.t_Mvv_alt : B.t_Mvv) + (size_t)c * TP;
       // fresh: Mvv = v_old v_old' was formed before the proposal; v_old is still unlist()
       // of the state `s`, so recompute it from s here (same products).
       double vold[R];
@@ -924,7 +993,7 @@ struct Smp {
       for (int u = 0; u < NT; ++u) lt[u] = (!fresh && u * G + g.lane < TP) ? Mvv[u * G + g.lane] : 0.0;
       // slot t = u G + lane: HBM and LDS addresses are the lane's base + a constant per u
       // (immediate offsets), the fresh / steady choice is made once outside the slot loop
-      double* const Mvv_l = Mvv + g.lane;
+      double* const Mvv_l = Mvv_w + g.lane;
       double* const mat_l = mat + g.lane;
       auto slots = [&](auto fresh_c) {
         constexpr bool FRESH = decltype(fresh_c)::value;
@@ -966,51 +1035,52 @@ struct Smp {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         int e = r * G + g.lane;
-        if (e < d) B.t_Mv[(size_t)c * DP + e] = mv[r];
+        if (e < d) ((dual && (m & 1)) ? B.t_Mv_alt : B.t_Mv)[(size_t)c * DP + e] = mv[r];
       }
       if (g.lane == 0) { B.t_m[c] = m; B.t_flags[c] = fl; }
       M::relist(B, s, g, v);
       M::stash(lds, s, g.lane);
-      int* pks = (int*)z2s;  // pivot order (group-uniform values), LDS
       grp_sync();
       MMB_PROF_MARK(4, g.lane)
-      int rank;
-      int redo = 0;
-      const bool carry = CARRY && B.t_xtag != nullptr && B.sigl_diag;
-      int pe = 0;
-      if constexpr (G == 32 && R == 1)
-        rank = pchol32(d, mat, (double*)ia, pks, g, &pe, carry ? &B : nullptr, A, c, chain, it, b, m, &redo);
-      else
-        rank = pchol(d, mat, (double*)ia, pks, g);
-      grp_sync();
-      MMB_PROF_MARK(5, g.lane)
-      if (B.t_astat != nullptr) amm_count(B, c, d, rank, redo, g);
-      if (rank == d) {
-        double* Ls = B.t_Ls + (size_t)c * TP;
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-          if (u * G + g.lane < T) Ls[u * G + g.lane] = mat[u * G + g.lane];
-        uint8_t* pv = B.t_piv + (size_t)c * DP;
-        if constexpr (POSFORM) {
-          if (g.lane < d) pv[g.lane] = (uint8_t)pe;  // position of element lane
-        } else {
-          for (int k = g.lane; k < d; k += G) pv[k] = (uint8_t)pks[k];
-        }
-        if (g.lane == 0) B.t_flags[c] = fl | 4;
-      }
-      M::unstash(lds, s, g.lane);
-      grp_sync();
-      MMB_PROF_MARK(6, g.lane)
-      return;
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int e = r * G + g.lane;
-      if (e < d) B.t_Mv[(size_t)c * DP + e] = mv[r];
-    }
-    if (g.lane == 0) { B.t_m[c] = m; B.t_flags[c] = fl; }
+    }  // !recover
+    int rank;
+    int redo = 0;
+    int pe = 0;
+    if constexpr (G == 32 && R == 1)
+      rank = pchol32(d, mat, (double*)ia, pks, g, &pe, (carry && !recover) ? &B : nullptr, A, c, chain, it, b, m, &redo,
+                     !lazy || recover);
+    else
+      rank = pchol(d, mat, (double*)ia, pks, g);
     grp_sync();
-    M::relist(B, s, g, v);
+    MMB_PROF_MARK(5, g.lane)
+    if (!recover && B.t_astat != nullptr) amm_count(B, c, d, rank, redo, g);
+    if (rank == d && (recover ? rec : !lazy)) {
+      double* Ls = B.t_Ls + (size_t)c * TP;
+#pragma unroll
+      for (int u = 0; u < NT; ++u)
+        if (u * G + g.lane < T) Ls[u * G + g.lane] = mat[u * G + g.lane];
+      uint8_t* pv = B.t_piv + (size_t)c * DP;
+      if constexpr (POSFORM) {
+        if (g.lane < d) pv[g.lane] = (uint8_t)pe;  // position of element lane
+      } else {
+        for (int k = g.lane; k < d; k += G) pv[k] = (uint8_t)pks[k];
+      }
+    }
+    if constexpr (!CARRY) {
+      if (rank == d && g.lane == 0) B.t_flags[c] = fl | 4;
+    } else {
+      if (recover) {
+        if (rec && g.lane == 0) B.t_flags[c] = (fl | 4) & ~STALE;
+        rec = false;
+      } else {
+        if (rank == d && g.lane == 0) B.t_flags[c] = lazy ? (fl | 4 | STALE) : ((fl | 4) & ~STALE);
+        rec = (fl & STALE) != 0 && rank < d;  // the caller runs the block again at once
+      }
+    }
+    M::unstash(lds, s, g.lane);
+    grp_sync();
+    MMB_PROF_MARK(6, g.lane)
   }
 
   // ---------------------------------------------------------------- Slice

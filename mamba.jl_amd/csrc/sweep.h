@@ -92,6 +92,10 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
   // needs one whose variance node was written since the last pass (models.h prep_pass); all
   // stale here, so no value crosses a launch
   typename M::PrepCache pk = M::prep_cache(lds);
+  // AMM lazy factor store (samplers.h amm): set by an update whose chain has to rebuild the factor
+  // of the update before; the block loop then visits the block a second time at once, so the
+  // rebuild runs through the one copy of the factorization
+  bool amm_rec = false;
   for (int step = 0; step < A.n_iters; ++step) {
     const int64_t it = A.iter0 + 1 + step;
 #ifdef MMB_PHASE_PROF
@@ -125,7 +129,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
           break;
         case MMB_SAMPLER_AMM:
           if constexpr ((KINDS >> MMB_SAMPLER_AMM) & 1u) S::amm(A, B, c, chain, it, b, rn, ru, adapt, s, l, g, lds,
-                                                                        G == 32 ? S::lane_value(pre, pre0 + b) : 0.0, pk);
+                                                                        G == 32 ? S::lane_value(pre, pre0 + b) : 0.0, pk,
+                                                                        amm_rec);
           break;
         case MMB_SAMPLER_SLICE:
           if constexpr ((KINDS >> MMB_SAMPLER_SLICE) & 1u) {
@@ -156,6 +161,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
           break;
       }
       M::prep_wrote(pk, B);
+      if constexpr (S::CARRY && ((KINDS >> MMB_SAMPLER_AMM) & 1u) != 0u) {
+        if (__builtin_expect(__ballot(amm_rec) != 0, 0)) --b;  // (wave-uniform; rare: a rounding event)
+      }
     }
 #ifdef MMB_PHASE_PROF
     if ((threadIdx.x & 63) == 0) {
