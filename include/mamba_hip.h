@@ -69,7 +69,7 @@ typedef enum {
 
 /* node ids (Stochastic nodes that can appear in a sampling block) */
 enum { MMB_LINE_BETA = 0, MMB_LINE_S2 = 1,
-       MMB_LINE_Y = 2 /* the observed node: valid in the node lists of mmb_draws_logpdf and its kin only */ };
+       MMB_LINE_Y = 2 /* the observed node: valid in the node lists of mmb_draws_logpdf, mmb_draws_predict and their kin only */ };
 enum {
   MMB_RATS_S2_C = 0, MMB_RATS_ALPHA = 1, MMB_RATS_MU_ALPHA = 2, MMB_RATS_S2_ALPHA = 3,
   MMB_RATS_BETA = 4, MMB_RATS_MU_BETA = 5, MMB_RATS_S2_BETA = 6
@@ -403,6 +403,46 @@ int mmb_draws_logpdf(mmb_engine* e, int nnodes, const int32_t* nodes,
 int mmb_draws_deviance(mmb_engine* e, int nnodes, const int32_t* nodes, double shift, double* out /* K x 2 */);
 int mmb_logpdf_at(mmb_engine* e, int nnodes, const int32_t* nodes,
                   const double* x /* pmon, one point in monitored-column order */, double* lp);
+
+/* Posterior predictive draws of the observed nodes on the device-kept draws (predict.hip):
+ * predict(mc, nodekeys) (src/output/modelstats.jl:71-102).  `nodes` lists 1 <= nnodes <= MMB_IR_MAX_TERMS
+ * observed (fixed) Stochastic node ids (line: MMB_LINE_Y only; node IR: indices of mmb_ir_model.nodes);
+ * P is the summed length of the listed nodes, column j counting their elements in list order.  For kept
+ * row i and local chain k the value of column j is one variate of the node's distribution, its parameters
+ * evaluated on that draw as mmb_draws_logpdf evaluates them, and it is a pure function of (seed,
+ * chain_offset + k, iteration start + i*thin, node id n, element e): it does not depend on sharding, row
+ * chunking, tile size or call order.  Philox counter and key as everywhere (mmb_math.h): key = seed,
+ * ctr.w = global chain id, ctr.z = (uint32)(start + i*thin), ctr.y = block*16 + substream, with blocks no
+ * sampler uses (those are < 8): the node block PB(n) = 256 + n and, for the gamma-based families, the
+ * element block GB(n, e) = (n + 1)*65536 + e (n < 4095 and 2*len <= 65536, else MMB_E_UNSUPPORTED).
+ *   Normal, IsoNormal  a + b z, z = normal #e of (PB, MMB_SUB_NORMAL)
+ *   Bernoulli          u < p ? 1 : 0, u = uniform #e of (PB, MMB_SUB_UNIFORM); Exponential(t) -t log1p(-u);
+ *   Uniform(lo, hi)    lo + (hi - lo) u
+ *   Binomial(n, p)     trials in ceil(n/512) chunks of at most 512, chunk c with uniform #(c*len + e), each
+ *                      by sequential-search inversion on min(p, 1 - p) (mirrored for p > 1/2), summed;
+ *                      n an integer in [0, 2^20], else NaN
+ *   Poisson(lambda)    max(1, ceil(lambda/256)) equal pieces, piece c with uniform #(c*len + e), each by
+ *                      sequential-search inversion (at most 4096 steps), summed; more than 64 pieces: NaN
+ *   Gamma(k, t) t G(k), InverseGamma(a, b) b / G(a), Beta(a, b) G1/(G1 + G2) with G1 = G(a) on GB(n, e) and
+ *                      G2 = G(b) on GB(n, len + e); G = mmb_gamma_any on MMB_SUB_GAMMA_N / _U from index 0
+ * A parameter that is not finite or outside the family's domain (sigma < 0, p outside [0, 1], lambda < 0,
+ * shape or scale <= 0, hi < lo) gives NaN for that element and draws nothing: every loop ends on any draws.
+ * Validation as mmb_draws_logpdf's (unmonitored parent: MMB_E_ARG naming the node id; hand-lowered rats
+ * and logistic: MMB_E_UNSUPPORTED; no device-kept draws: MMB_E_STATE), and: a listed node that is not
+ * observed is MMB_E_ARG; thin >= 1, start >= 0, 0 <= i0 < i1 <= mmb_num_kept, else MMB_E_ARG; a result tile
+ * of 8 chains that does not fit the LDS beside the state images is MMB_E_UNSUPPORTED.  All of it precedes any
+ * launch; none of these calls touches chain state, tune, iteration counter, draws, hpd tails or chain order.
+ * mmb_draws_predict: rows [i0, i1) of the kept draws, out[(i - i0) + (i1 - i0)*(j + P*k)]; row i always has
+ *   iteration start + i*thin (i the kept-row index), so a window equals the same rows of the full call.
+ * mmb_draws_predict_moments: over all kept rows, out[(k*P + j)*2] = sum_i (yhat - shift[j]) and
+ *   out[(k*P + j)*2 + 1] = sum_i (yhat - shift[j])^2 in row order; the values stay on the device.
+ *   Non-finite values propagate.  Additive across chains and GPUs for a common shift.
+ * mmb_predict_width: P of a node list (after the same validation). */
+int mmb_draws_predict(mmb_engine* e, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start, int64_t thin,
+                      int64_t i0, int64_t i1, double* out /* (i1-i0) x P x K, Chains order */);
+int mmb_draws_predict_moments(mmb_engine* e, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start,
+                              int64_t thin, const double* shift /* P */, double* out /* K x P x 2 */);
+int mmb_predict_width(mmb_engine* e, int nnodes, const int32_t* nodes, int64_t* P);
 
 /* Upload draws: the inverse of mmb_get_draws. `draws` is nkept x p x K column-major (the
  * Chains value layout, iteration fastest); it is transposed into the device draw buffer, which

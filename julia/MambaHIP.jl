@@ -202,6 +202,31 @@ function logpdf_at(e, nodes::Vector{Int32}, x::Vector{Float64})
               e, length(nodes), nodes, x, lp), e); lp[1]
 end
 
+# predict(mc, nodekeys) (modelstats.jl:71-102) on one engine's device-kept draws: `nodes` are 0-based
+# observed node ids; kept row i has iteration start + i*thin, a value is a function of (seed, global
+# chain id, iteration, node id, element) only
+function predict_width(e, nodes::Vector{Int32})
+  P = zeros(Int64, 1)
+  check(ccall((:mmb_predict_width, libmambahip), Cint, (Ptr{Void}, Cint, Ptr{Int32}, Ptr{Int64}),
+              e, length(nodes), nodes, P), e); Int(P[1])
+end
+function draws_predict(e, nodes::Vector{Int32}, seed::Integer, start::Integer, thin::Integer,
+                       i0::Integer=0, i1::Integer=num_kept(e))       # (i1 - i0) x P x chains
+  out = zeros(Float64, Int(i1 - i0), predict_width(e, nodes), Int(num_chains(e)))
+  check(ccall((:mmb_draws_predict, libmambahip), Cint,
+              (Ptr{Void}, Cint, Ptr{Int32}, UInt64, Int64, Int64, Int64, Int64, Ptr{Float64}),
+              e, length(nodes), nodes, seed, start, thin, i0, i1, out), e); out
+end
+function draws_predict_moments(e, nodes::Vector{Int32}, seed::Integer, start::Integer, thin::Integer,
+                               shift::Vector{Float64})                # 2 x P x chains: sums of yhat - shift and its square
+  P = predict_width(e, nodes)
+  length(shift) == P || throw(ArgumentError("shift must hold one value per predicted column"))
+  out = zeros(Float64, 2, P, Int(num_chains(e)))
+  check(ccall((:mmb_draws_predict_moments, libmambahip), Cint,
+              (Ptr{Void}, Cint, Ptr{Int32}, UInt64, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+              e, length(nodes), nodes, seed, start, thin, shift, out), e); out
+end
+
 # the one collective (mmb_comm_*): RCCL over xGMI inside the library
 function comm_id()
   id = zeros(UInt8, MMB_COMM_ID_BYTES)

@@ -14,6 +14,7 @@ from .diag import (autocor, changerate_sharded, geweke_windows, geweke_z, geweke
                    pcramer, rafterydiag)
 from .summary import hpd_sharded, pool_summary, quantile_sharded, summarystats_sharded  # noqa: F401
 from .modelstats import dic, dic_sharded, logpdf, logpdf_sharded  # noqa: F401
+from .modelstats import predict, predict_moments_sharded, predict_sharded, predict_summary  # noqa: F401
 from .mcmc import Chains, Engine, mcmc, mcmc_restart, read, write  # noqa: F401
 from .model import line, logistic, rats  # noqa: F401
 from .samplers import (AMM, AMWG, HMC, MALA, NUTS, ArgumentError, Gibbs, Multivariate, Sampler,  # noqa: F401

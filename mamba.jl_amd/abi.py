@@ -131,6 +131,9 @@ def _declare(lib):
         "mmb_draws_logpdf": (C.c_int, [P, C.c_int, C.POINTER(I32), D]),
         "mmb_draws_deviance": (C.c_int, [P, C.c_int, C.POINTER(I32), C.c_double, D]),
         "mmb_logpdf_at": (C.c_int, [P, C.c_int, C.POINTER(I32), D, D]),
+        "mmb_draws_predict": (C.c_int, [P, C.c_int, C.POINTER(I32), C.c_uint64, I64, I64, I64, I64, D]),
+        "mmb_draws_predict_moments": (C.c_int, [P, C.c_int, C.POINTER(I32), C.c_uint64, I64, I64, D, D]),
+        "mmb_predict_width": (C.c_int, [P, C.c_int, C.POINTER(I32), C.POINTER(I64)]),
         "mmb_sync": (C.c_int, [P]),
         "mmb_kernel_time": (C.c_int, [P, D, C.POINTER(I64), C.POINTER(I64)]),
         "mmb_state_bytes": (C.c_int, [P, D]),

@@ -22,6 +22,7 @@
 #include "logistic.h"
 #include "ir.h"
 #include "ir_jit.h"
+#include "predict_math.h"
 
 #include <rccl/rccl.h>
 
@@ -68,6 +69,15 @@ hipError_t mmb_launch_modelstats(int model, const SweepArgs& A, int nvalues, int
                                  const double* draws, int nnodes, const int32_t* nodes, const int32_t* col,
                                  const int32_t* slot, int ncols, double* lp, hipStream_t st);
 hipError_t mmb_launch_deviance(int64_t rows, int K, const double* lp, double shift, double* acc, hipStream_t st);
+
+// predict.hip
+int mmb_predict_tile(int nvalues, int stack, int P, int* S, int* RS);
+hipError_t mmb_launch_predict(int model, const SweepArgs& A, int nvalues, int stack, int64_t n, int K, int pmon,
+                              const double* draws, int nnodes, const int32_t* nodes, const int32_t* col0, int P,
+                              const int32_t* col, const int32_t* slot, int ncols, uint64_t seed, int64_t it0,
+                              int64_t thin, double* yhat, hipStream_t st);
+hipError_t mmb_launch_predict_moments(int64_t rows, int K, int P, const double* yhat, const double* shift, double* acc,
+                                      hipStream_t st);
 
 hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
 
@@ -2345,14 +2355,15 @@ struct MsPlan {
   std::vector<int32_t> col, slot;
 };
 
-static int ms_plan(mmb_engine* e, int nnodes, const int32_t* nodes, bool need_draws, MsPlan& pl) {
+static int ms_plan(mmb_engine* e, int nnodes, const int32_t* nodes, bool need_draws, MsPlan& pl,
+                   const char* what = "logpdf") {
   if (e->model == MMB_MODEL_RATS)
-    return fail(e, MMB_E_UNSUPPORTED, "logpdf: the hand-lowered rats model monitors 3 of its 65 values (s2_c, mu_beta, "
+    return fail(e, MMB_E_UNSUPPORTED, "%s: the hand-lowered rats model monitors 3 of its 65 values (s2_c, mu_beta, "
                 "alpha0): alpha and beta are not in the chains, so the nodes cannot be relisted from the draws "
-                "(use the node-IR rats model with alpha, beta and the hyper-parameters monitored)");
+                "(use the node-IR rats model with alpha, beta and the hyper-parameters monitored)", what);
   if (e->model == MMB_MODEL_LOGISTIC)
-    return fail(e, MMB_E_UNSUPPORTED, "logpdf: the logistic model evaluates its likelihood through its own batched "
-                "engine; its model statistics are not lowered yet");
+    return fail(e, MMB_E_UNSUPPORTED, "%s: the logistic model evaluates its likelihood through its own batched "
+                "engine; its model statistics are not lowered yet", what);
   if (!e->d_vals || (need_draws && e->n_kept < 1))
     return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
   if (nnodes < 1 || nnodes > MMB_IR_MAX_TERMS) return fail(e, MMB_E_ARG, "1 <= nnodes <= %d", MMB_IR_MAX_TERMS);
@@ -2495,6 +2506,130 @@ int mmb_logpdf_at(mmb_engine* e, int nnodes, const int32_t* nodes, const double*
   (void)hipStreamSynchronize(e->stream);
   (void)hipFree(d_x);
   return rc;
+}
+
+// ---------------------------------------------------------------- posterior prediction (modelstats.jl:71-102)
+// The plan of a predict call: the node list's plan (ms_plan), the first result column of every list
+// entry and the result width P.  Everything is validated here, before any launch.
+struct PrPlan {
+  MsPlan ms;
+  std::vector<int32_t> col0;
+  int P = 0;
+};
+
+static int pr_plan(mmb_engine* e, int nnodes, const int32_t* nodes, PrPlan& pl) {
+  if (int rc = ms_plan(e, nnodes, nodes, true, pl.ms, "predict")) return rc;
+  if (e->model == MMB_MODEL_LINE) {
+    if (nnodes != 1 || nodes[0] != MMB_LINE_Y)
+      return fail(e, MMB_E_ARG, "predict: y (MMB_LINE_Y) is the only observed node of the line model");
+    pl.col0.assign(1, 0);
+    pl.P = 5;
+    return 0;
+  }
+  int64_t P = 0;
+  for (int a = 0; a < nnodes; ++a) {
+    const mmb_ir_node& N = e->ir_nodes[nodes[a]];
+    if (!N.fixed) return fail(e, MMB_E_ARG, "node id %d is not an observed Stochastic node of the model", nodes[a]);
+    const bool gam = N.family == MMB_IR_GAMMA || N.family == MMB_IR_INVGAMMA || N.family == MMB_IR_BETA;
+    if (gam && !mmb_pr_gblock_ok(nodes[a], N.len))
+      return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d (length %d) does not fit the element blocks of the "
+                  "gamma streams (node id < 4095, 2 * length <= 65536)", nodes[a], N.len);
+    pl.col0.push_back((int32_t)P);
+    P += N.len;
+  }
+  int S, RS;
+  if (P > MMB_IR_MAX_VALUES * 4 || mmb_predict_tile(e->P, e->ir_stack, (int)P, &S, &RS) == 0)
+    return fail(e, MMB_E_UNSUPPORTED, "predict: a tile of 8 chains (%d state values and %lld predicted values each) "
+                "does not fit the 64 KiB of LDS: predict fewer nodes per call", e->P, (long long)P);
+  pl.P = (int)P;
+  return 0;
+}
+
+// doubles of the device scratch of predicted values per pass; MMB_PREDICT_CHUNK_ROWS (tests) caps its rows
+constexpr int64_t PR_CHUNK = 8ll << 20;
+
+// shared body over the kept rows [i0, i1): out (host, Chains order, (i1 - i0) x P x K) and / or acc (host,
+// K x P x 2 sums about `shift`, P values)
+static int pr_run(mmb_engine* e, const char* what, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start,
+                  int64_t thin, int64_t i0, int64_t i1, double* out, const double* shift, double* acc) {
+  PrPlan pl;
+  if (int rc = pr_plan(e, nnodes, nodes, pl)) return rc;
+  if (thin < 1 || start < 0) return fail(e, MMB_E_ARG, "%s: thin >= 1 and start >= 0", what);
+  if (i0 < 0 || i1 <= i0 || i1 > e->n_kept)
+    return fail(e, MMB_E_ARG, "window [%lld, %lld) is not inside the %lld kept draws", (long long)i0, (long long)i1,
+                (long long)e->n_kept);
+  HIPCHK(e, hipSetDevice(e->device));
+  SweepArgs A;
+  fill_args(e, A);
+  const int K = (int)e->K, P = pl.P;
+  const int64_t nw = i1 - i0;
+  int64_t crows = std::max<int64_t>(1, std::min<int64_t>(nw, PR_CHUNK / ((int64_t)P * K)));
+  if (const char* s = std::getenv("MMB_PREDICT_CHUNK_ROWS")) crows = std::max<int64_t>(1, std::min<int64_t>(crows, std::atoll(s)));
+  int32_t* d_tab = nullptr;
+  double *d_y = nullptr, *d_acc = nullptr, *d_shift = nullptr;
+  const size_t nc = pl.ms.col.size();
+  const size_t nacc = (size_t)2 * K * P;
+  hipError_t st = hipSuccess;
+  if (nc) {
+    st = hipMalloc(&d_tab, 2 * nc * sizeof(int32_t));
+    if (st == hipSuccess)
+      st = hipMemcpyAsync(d_tab, pl.ms.col.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess)
+      st = hipMemcpyAsync(d_tab + nc, pl.ms.slot.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+  }
+  if (st == hipSuccess) st = hipMalloc(&d_y, (size_t)crows * P * K * sizeof(double));
+  if (st == hipSuccess && acc) {
+    st = hipMalloc(&d_acc, nacc * sizeof(double));
+    if (st == hipSuccess) st = hipMemsetAsync(d_acc, 0, nacc * sizeof(double), e->stream);
+    if (st == hipSuccess) st = hipMalloc(&d_shift, (size_t)P * sizeof(double));
+    if (st == hipSuccess) st = hipMemcpyAsync(d_shift, shift, (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream);
+  }
+  std::vector<double> h;
+  if (out) h.resize((size_t)crows * P * K);
+  for (int64_t r0 = i0; r0 < i1 && st == hipSuccess; r0 += crows) {
+    const int64_t rows = std::min(crows, i1 - r0);
+    st = mmb_launch_predict(e->model, A, e->P, e->ir_stack, rows, K, e->pmon, e->d_draws + (size_t)r0 * e->pmon * K,
+                            nnodes, nodes, pl.col0.data(), P, d_tab, d_tab ? d_tab + nc : nullptr, (int)nc, seed,
+                            start + r0 * thin, thin, d_y, e->stream);
+    if (st == hipSuccess && acc) st = mmb_launch_predict_moments(rows, K, P, d_y, d_shift, d_acc, e->stream);
+    if (st == hipSuccess && out) {
+      st = hipMemcpyAsync(h.data(), d_y, (size_t)rows * P * K * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+      if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+      if (st == hipSuccess)
+        for (int64_t i = 0; i < rows; ++i)
+          for (int64_t j = 0; j < P; ++j)
+            for (int64_t k = 0; k < K; ++k) out[(r0 - i0 + i) + nw * (j + (int64_t)P * k)] = h[((size_t)i * P + j) * K + k];
+    }
+  }
+  if (st == hipSuccess && acc) st = hipMemcpyAsync(acc, d_acc, nacc * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+  const hipError_t sy = hipStreamSynchronize(e->stream);  // also after a failure: nothing is freed under a kernel
+  if (st == hipSuccess) st = sy;
+  if (d_tab) (void)hipFree(d_tab);
+  if (d_y) (void)hipFree(d_y);
+  if (d_acc) (void)hipFree(d_acc);
+  if (d_shift) (void)hipFree(d_shift);
+  if (st != hipSuccess) return fail(e, MMB_E_HIP, "%s: %s", what, hipGetErrorString(st));
+  return 0;
+}
+
+int mmb_predict_width(mmb_engine* e, int nnodes, const int32_t* nodes, int64_t* P) {
+  if (!e || !nodes || !P) return fail(e, MMB_E_ARG, "null argument");
+  PrPlan pl;
+  if (int rc = pr_plan(e, nnodes, nodes, pl)) return rc;
+  *P = pl.P;
+  return 0;
+}
+
+int mmb_draws_predict(mmb_engine* e, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start, int64_t thin,
+                      int64_t i0, int64_t i1, double* out) {
+  if (!e || !nodes || !out) return fail(e, MMB_E_ARG, "null argument");
+  return pr_run(e, "draws_predict", nnodes, nodes, seed, start, thin, i0, i1, out, nullptr, nullptr);
+}
+
+int mmb_draws_predict_moments(mmb_engine* e, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start,
+                              int64_t thin, const double* shift, double* out) {
+  if (!e || !nodes || !shift || !out) return fail(e, MMB_E_ARG, "null argument");
+  return pr_run(e, "draws_predict_moments", nnodes, nodes, seed, start, thin, 0, e->n_kept, nullptr, shift, out);
 }
 
 // ---------------------------------------------------------------- per-chain diagnostics

@@ -21,38 +21,21 @@
 //   group makes the same trips (the butterflies and wave barriers need all lanes).
 //   LDS per workgroup = (T*S + 4*(stack + 1)*32) doubles; the host picks T = 32, 16 or 8 as the
 //   largest that keeps it within MS_LDS_BYTES (64 KiB: two workgroups per CU stay resident, and
-//   no opt-in for a larger dynamic allocation is needed).
+//   no opt-in for a larger dynamic allocation is needed).  The launch arguments and the load phase are
+//   in modelstats.h: predict.hip tiles the same way.
 //
 // ms_line_kernel (hand-lowered line): one thread per (row, chain), three coalesced loads; terms
 //   y = Mdl<line>::ylp, beta = the prior as Mdl<line>::logf forms it, s2 = d_iglogpdf(ig_c, s2, 0).
 //
 // ms_deviance_kernel: per chain, [sum_i (D - c), sum_i (D - c)^2] with D = -2 lp, in row order,
 //   continued over row chunks (the n x K values stay on the device; non-finite values propagate).
-#include "sweep.h"
+#include "modelstats.h"
 
-#define MS_THREADS 128
-#define MS_GROUPS (MS_THREADS / 32)
-#define MS_LDS_BYTES 65536
 #define MS_DEV_THREADS 64   // deviance reduction: one wavefront per workgroup spreads few chains over the CUs
 #define MS_DEV_ROWS 16      // its loads in flight per thread
 
 // LDS doubles of a workgroup with a tile of T chains
 static size_t ms_lds_doubles(int T, int S, int stack) { return (size_t)T * S + (size_t)MS_GROUPS * (stack + 1) * 32; }
-
-struct MsArgs {
-  int64_t n;             // rows of `draws`
-  int32_t K, pmon;       // chains, monitored columns
-  const double* draws;   // [n][pmon][K]
-  double* lp;            // [n][K]
-  int32_t nnodes;
-  int32_t nodes[MMB_IR_MAX_TERMS];
-  // node IR
-  const int32_t* col;    // [ncols] monitored column
-  const int32_t* slot;   // [ncols] its state slot
-  int32_t ncols;
-  int32_t T, S;          // tile chains, image stride (doubles)
-  int32_t stack;         // expression stack depth
-};
 
 __global__ __launch_bounds__(MS_THREADS) void ms_ir_kernel(const SweepArgs A, const MsArgs M) {
   extern __shared__ double ms_lds[];
@@ -65,17 +48,10 @@ __global__ __launch_bounds__(MS_THREADS) void ms_ir_kernel(const SweepArgs A, co
   const int T = M.T;
   const int64_t ktiles = ((int64_t)M.K + T - 1) / T;
   const int64_t ntiles = M.n * ktiles;
-  const int lc = t % T, cs = t / T, cstep = MS_THREADS / T;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t i = tile / ktiles;
     const int64_t k0 = (tile - i * ktiles) * T;
-    {
-      int64_t k = k0 + lc;
-      if (k > M.K - 1) k = M.K - 1;
-      const double* row = M.draws + (size_t)i * M.pmon * M.K + k;
-      double* dst = img + (size_t)lc * M.S;
-      for (int q = cs; q < M.ncols; q += cstep) dst[M.slot[q]] = row[(size_t)M.col[q] * M.K];
-    }
+    ms_load_tile(M, i, k0, t, img);
     __syncthreads();
     for (int c = grp; c < T; c += MS_GROUPS) {
       const double* vals = img + (size_t)c * M.S;

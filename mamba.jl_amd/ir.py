@@ -696,7 +696,10 @@ class _Lowering:
         m.parents = parents
         m._stats = {"stoch": list(m.stoch), "output": [n for n in m.fixed if n not in node_fixed_reads],
                     "parents": parents, "sampled": set(m.params),
-                    "monitored": {n for n in m.params if m.defs[n].monitor}, "ids": {n: ids[n] for n in m.stoch}}
+                    "monitored": {n for n in m.params if m.defs[n].monitor}, "ids": {n: ids[n] for n in m.stoch},
+                    "names": {n: [n] if (m.defs[n].dim == 0 and nodes[ids[n]].len == 1)
+                              else [f"{n}[{i + 1}]" for i in range(nodes[ids[n]].len)] for n in m.stoch},
+                    "observed": {n: np.array(m.fixed_vals[n], dtype=np.float64).ravel() for n in m.fixed}}
         keep = {"nodes": nodes, "code": np.asarray(self.code, dtype=np.int32),
                 "consts": np.asarray(self.consts + [0.0], dtype=np.float64),
                 "pool": np.asarray(self.pool + [0.0], dtype=np.float64),

@@ -279,6 +279,40 @@ class Engine:
         self._chk(self.lib.mmb_logpdf_at(self.h, int(ids.size), p, abi.dptr(x), C.byref(lp)))
         return lp.value
 
+    # posterior predictive draws of the observed nodes (modelstats.py maps names and closes the moments)
+    def predict_width(self, nodes):
+        """P: the summed length of the listed observed nodes (mmb_predict_width)."""
+        ids, p = self._node_list(nodes)
+        P = C.c_int64()
+        self._chk(self.lib.mmb_predict_width(self.h, int(ids.size), p, C.byref(P)))
+        return int(P.value)
+
+    def draws_predict(self, nodes, seed, start, thin, i0=0, i1=None):
+        """(i1 - i0) x P x K: one variate of every element of the listed observed nodes at the kept
+        draws [i0, i1) (default: all), parameters evaluated on the draw (mmb_draws_predict,
+        modelstats.jl:71-102).  Kept row i has iteration start + i * thin; a value is a function of
+        (seed, global chain id, iteration, node id, element) only."""
+        ids, p = self._node_list(nodes)
+        i1 = self.num_kept() if i1 is None else int(i1)
+        P = self.predict_width(ids)
+        out = np.empty((max(i1 - int(i0), 0), P, self.K), order="F")
+        self._chk(self.lib.mmb_draws_predict(self.h, int(ids.size), p, C.c_uint64(int(seed)), int(start), int(thin),
+                                             int(i0), i1, abi.dptr(out)))
+        return out
+
+    def draws_predict_moments(self, nodes, seed, start, thin, shift):
+        """K x P x 2: per chain and predicted column [sum_i (yhat - shift_j), sum_i (yhat - shift_j)^2]
+        over the kept draws, in row order (mmb_draws_predict_moments); the values stay on the device."""
+        ids, p = self._node_list(nodes)
+        P = self.predict_width(ids)
+        shift = np.ascontiguousarray(shift, dtype=np.float64).reshape(-1)
+        if shift.size != P:
+            raise ArgumentError(f"the shift must have {P} values, got {shift.size}")
+        out = np.empty((self.K, P, 2))
+        self._chk(self.lib.mmb_draws_predict_moments(self.h, int(ids.size), p, C.c_uint64(int(seed)), int(start),
+                                                     int(thin), abi.dptr(shift), abi.dptr(out)))
+        return out
+
     def set_draws(self, value):
         """Upload `value` (n x p x chains, the Chains layout) as the device-kept draws
         (mmb_set_draws, the inverse of `draws`): the device summaries then run on it."""
@@ -472,6 +506,21 @@ class Chains:
         labels, column labels), from the deviance of the output nodes on the device-kept draws."""
         from .modelstats import dic
         return dic(self)
+
+
+    def predict(self, nodekeys=None, seed=None, rows=None):
+        """predict(mc[, nodekeys]) (modelstats.jl:71-102): posterior predictive draws of the observed
+        output nodes (default: all of them) at every kept draw, a Chains n x P x chains named like
+        names(m, nodekeys).  `seed` defaults to the seed of the chains; `rows` = (i0, i1) restricts
+        the call to the kept rows [i0, i1), whose values equal those rows of the full call."""
+        from .modelstats import predict
+        return predict(self, nodekeys, seed, rows)
+
+    def predict_summary(self, nodekeys=None, seed=None):
+        """(P x 2 [Mean, SD] of the predicted values pooled over draws and chains, names, column
+        labels): the moments are reduced on the device, the predicted values never leave it."""
+        from .modelstats import predict_summary
+        return predict_summary(self, nodekeys, seed)
 
 
 def mcmc(model, inputs, inits, iters, burnin=0, thin=1, chains=1, verbose=False, device=0,

@@ -154,7 +154,8 @@ def line():
     m = Model(abi.MMB_MODEL_LINE, nodes, 3, ["beta[1]", "beta[2]", "s2"], ["x", "y"])
     m._stats = {"stoch": ["y", "beta", "s2"], "output": ["y"],
                 "parents": {"y": {"beta", "s2"}, "beta": set(), "s2": set()}, "sampled": {"beta", "s2"},
-                "monitored": {"beta", "s2"}, "ids": {"beta": abi.MMB_LINE_BETA, "s2": abi.MMB_LINE_S2, "y": abi.MMB_LINE_Y}}
+                "monitored": {"beta", "s2"}, "ids": {"beta": abi.MMB_LINE_BETA, "s2": abi.MMB_LINE_S2, "y": abi.MMB_LINE_Y},
+                "names": {"y": [f"y[{i + 1}]" for i in range(5)], "beta": ["beta[1]", "beta[2]"], "s2": ["s2"]}}
     return m
 
 

@@ -14,8 +14,10 @@ names2inds fails too).  One equivalence: the reference relists a *monitored* Log
 chain; here a Logical is recomputed from its parents through the inlined expression -- the same
 function of the draw, but its parents must be monitored.
 
-Not here: predict (modelstats.jl:71-102) draws rand(node) per kept row and needs random streams
-of its own.
+predict(mc, nodekeys) (modelstats.jl:71-102) draws rand(node) of the observed output nodes at every
+kept draw.  The reference draws from Julia's global RNG; here a predicted value is a pure function
+of (seed, global chain id, iteration of the kept row, node id, element) on Philox streams of its own
+(predict.hip, include/mamba_hip.h), so it does not depend on sharding, chunking or call order.
 """
 import re
 
@@ -25,6 +27,7 @@ from .samplers import ArgumentError
 
 DIC_ROWS = ["pD", "pV"]
 DIC_COLS = ["DIC", "Effective Parameters"]
+PREDICT_COLS = ["Mean", "SD"]
 
 
 def _keys(model, nodekeys, default):
@@ -131,3 +134,95 @@ def dic(sim):
     if sim.model is None:
         raise ArgumentError("dic needs the model of the chains")
     return dic_sharded(sim._device_engine(), sim.model)
+
+
+# ---------------------------------------------------------------- predict (modelstats.jl:71-102)
+def predict_keys(model, nodekeys=None):
+    """The node list of a predict call: `nodekeys` (default keys(m, :output), may be one name), every
+    one an output node, or the reference's ArgumentError (modelstats.jl:78-82, its message verbatim,
+    the typo "nodess" included)."""
+    nodekeys = _keys(model, nodekeys, "output")
+    outputs = model.keys("output")
+    if not all(k in outputs for k in nodekeys):
+        raise ArgumentError("nodekeys are not all observed Stochastic nodess : " + ", ".join(outputs))
+    return nodekeys
+
+
+def predict_names(model, nodekeys):
+    """names(m, nodekeys): y[1], y[2], ... per element, a scalar node by its bare name."""
+    t = model.stats_table()
+    return [nm for k in nodekeys for nm in t["names"][k]]
+
+
+def _observed(model, nodekeys):
+    """The listed nodes' observed values, in result-column order."""
+    obs = model.stats_table().get("observed", {})
+    parts = []
+    for k in nodekeys:
+        v = obs[k] if k in obs else (model.inputs or {}).get(k)
+        if v is None:
+            raise ArgumentError(f"no observed values for node {k}: set the model's inputs")
+        parts.append(np.asarray(v, dtype=np.float64).ravel())
+    return np.concatenate(parts)
+
+
+def _predict_seed(engine, seed):
+    return int(engine.seed if seed is None else seed)
+
+
+def predict_sharded(engine, model, nodekeys=None, seed=None, start=1, thin=1, rows=None):
+    """predict(mc, nodekeys) of this engine's kept draws: (value n x P x K, names).  Kept row i has
+    iteration start + i * thin; `rows` = (i0, i1) gives the kept rows [i0, i1) only.  Global chain
+    ids key the streams, so the shards of a run predict what one engine over all chains predicts."""
+    keys = predict_keys(model, nodekeys)
+    ids = node_ids(model, keys)
+    i0, i1 = (0, engine.num_kept()) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= i0 < i1 <= engine.num_kept():
+        raise ArgumentError(f"rows [{i0}, {i1}) are not inside the {engine.num_kept()} kept draws")
+    value = _engine_call(model, engine.draws_predict, ids, _predict_seed(engine, seed), int(start), int(thin), i0, i1)
+    return value, predict_names(model, keys)
+
+
+def predict(sim, nodekeys=None, seed=None, rows=None):
+    """predict(mc[, nodekeys]) (modelstats.jl:71-102): a Chains n x P x K of posterior predictive
+    draws, named names(m, nodekeys), with `sim`'s start (shifted to the first of `rows`), thin,
+    chains and model.  `seed` defaults to the seed the chains were initialised with."""
+    from .mcmc import Chains
+    if sim.model is None:
+        raise ArgumentError("predict needs the model of the chains")
+    keys = predict_keys(sim.model, nodekeys)
+    node_ids(sim.model, keys)  # argument errors come before the engine is asked for
+    value, names = predict_sharded(sim._device_engine(), sim.model, keys, seed, sim.start, sim.thin, rows)
+    i0 = 0 if rows is None else int(rows[0])
+    return Chains(value, names, sim.start + i0 * sim.thin, sim.thin, sim.chains, sim.model, None)
+
+
+def predict_moments_sharded(engine, model, nodekeys=None, allreduce_sum=None, seed=None, start=1, thin=1):
+    """Pooled P x [Mean, SD] of the predicted values over every chain of every rank; they never leave
+    the device.  The per-chain sums of (yhat - y) and its square about the node's observed data y (a
+    shift every rank shares, near the values, so nothing cancels) come from mmb_draws_predict_moments;
+    one all-reduce of [S1, S2, N]: Mean = y + S1 / N, SD = sqrt((S2 - S1^2 / N) / (N - 1))."""
+    red = (lambda v: np.asarray(allreduce_sum(np.asarray(v, dtype=np.float64)), dtype=np.float64)) \
+        if allreduce_sum is not None else (lambda v: np.asarray(v, dtype=np.float64))
+    keys = predict_keys(model, nodekeys)
+    ids = node_ids(model, keys)
+    n, K = engine.num_kept(), engine.K
+    if n < 1:
+        raise ArgumentError("predict runs on the device-kept draws: sample with keep_device=True")
+    shift = _observed(model, keys)
+    acc = np.asarray(_engine_call(model, engine.draws_predict_moments, ids, _predict_seed(engine, seed), int(start),
+                                  int(thin), shift), dtype=np.float64)
+    P = acc.shape[1]
+    tot = red(np.concatenate([acc[:, :, 0].sum(0), acc[:, :, 1].sum(0), [float(n) * K]]))
+    S1, S2, N = tot[:P], tot[P:2 * P], float(tot[2 * P])
+    var = (S2 - S1 * S1 / N) / (N - 1.0) if N > 1.0 else np.full(P, np.nan)
+    return np.column_stack([shift + S1 / N, np.sqrt(var)])
+
+
+def predict_summary(sim, nodekeys=None, seed=None):
+    """(P x 2 [Mean, SD] of predict(mc, nodekeys) pooled over draws and chains, names, ["Mean", "SD"])."""
+    if sim.model is None:
+        raise ArgumentError("predict needs the model of the chains")
+    keys = predict_keys(sim.model, nodekeys)
+    value = predict_moments_sharded(sim._device_engine(), sim.model, keys, None, seed, sim.start, sim.thin)
+    return value, predict_names(sim.model, keys), list(PREDICT_COLS)
