@@ -85,11 +85,18 @@ typedef enum {
   MMB_SAMPLER_GIBBS = 5, /* user Sampler(params, f): conjugate full conditional of the block's node,
                             e.g. doc/tutorial/line.jl:27-45 */
   MMB_SAMPLER_HMC = 6,   /* src/samplers/hmc.jl:47-65 */
-  MMB_SAMPLER_MALA = 7   /* src/samplers/mala.jl:43-58 */
+  MMB_SAMPLER_MALA = 7,  /* src/samplers/mala.jl:43-58 */
+  MMB_SAMPLER_RWM = 8    /* src/samplers/rwm.jl:49-71 (additive: the ABI version is unchanged) */
 } mmb_sampler_kind;
 
 typedef enum { MMB_ADAPT_ALL = 0, MMB_ADAPT_BURNIN = 1, MMB_ADAPT_NONE = 2 } mmb_adapt;
 typedef enum { MMB_SLICE_MULTIVARIATE = 0, MMB_SLICE_UNIVARIATE = 1 } mmb_slice_form;
+/* RWM proposal(0.0, 1.0): Normal or a SymDistributionType (src/distributions/extensions.jl:51-53);
+ * the standard variates are drawn as csrc/symdist.h says */
+typedef enum {
+  MMB_RWM_NORMAL = 0, MMB_RWM_SYMUNIFORM = 1, MMB_RWM_SYMTRIANGULAR = 2, MMB_RWM_EPANECHNIKOV = 3,
+  MMB_RWM_BIWEIGHT = 4, MMB_RWM_TRIWEIGHT = 5, MMB_RWM_COSINE = 6
+} mmb_rwm_proposal;
 
 /* One sampling block = one Sampler in Model.samplers (src/Mamba.jl:119-124). */
 /* Gradient of a NUTS / HMC / MALA block.  The reference differentiates logpdf! with Calculus
@@ -109,15 +116,15 @@ typedef struct {
   int32_t nnodes;                          /* number of nodes in `params` */
   int32_t nodes[MMB_MAX_NODES_PER_BLOCK];  /* node ids in block (params) order */
   int32_t adapt;                           /* AMWG/AMM: mmb_adapt (default :all) */
-  int32_t form;                            /* Slice: mmb_slice_form (default Multivariate) */
-  int32_t transform;                       /* Slice: transform flag (default false); AMWG/AMM/NUTS use true */
+  int32_t form;                            /* Slice: mmb_slice_form (default Multivariate); RWM: mmb_rwm_proposal */
+  int32_t transform;                       /* Slice: transform flag (default false); AMWG/AMM/NUTS/RWM use true */
   int32_t batchsize;                       /* AMWG batchsize (default 50) */
   double target;                           /* AMWG target (0.44) / NUTS target (0.6) */
   double beta;                             /* AMM beta (0.05) */
   double scale;                            /* AMM scale (2.38) */
   int32_t dim;                             /* unlisted block length (checked by mmb_create) */
   int32_t ntuning;                         /* length of `tuning` */
-  const double* tuning;                    /* AMWG sigma[dim] | Slice width[dim] | AMM Sigma[dim*dim] col-major
+  const double* tuning;                    /* AMWG sigma[dim] | Slice width[dim] | RWM scale[dim] | AMM Sigma[dim*dim] col-major
                                               | HMC/MALA Sigma[dim*dim] col-major, or none (SigmaL = I) */
   double epsilon;                          /* HMC/MALA step size (hmc.jl:13, mala.jl:12) */
   int32_t nsteps;                          /* HMC leapfrog steps L (hmc.jl:13) */
@@ -574,6 +581,11 @@ int mmb_amm_stats(mmb_engine* e, int64_t* out /* MMB_MAX_BLOCKS x MMB_AMM_STATS 
  * MMB_SLICE_EXACT=1 the one-candidate-at-a-time Slice shrink loop of the rats scalar blocks).
  * Both paths give the same draws; diagnostics only. */
 int mmb_amwg_stats(mmb_engine* e, int64_t* out /* 1 */);
+
+/* RWM counters since mmb_init_chains, per sampling block b (zero rows for non-RWM blocks), summed
+ * over the engine's chains: out[2 b] = block updates, out[2 b + 1] = accepted ones (rwm.jl:67-70).
+ * A user sizes `scale` from this acceptance rate (RWM does not adapt).  Diagnostics only. */
+int mmb_rwm_stats(mmb_engine* e, int64_t* out /* MMB_MAX_BLOCKS x 2 */);
 
 /* The lane-group slot -> chain table the next window will run with (K entries; the identity
  * when no ordering applies).  The 32-lane sweep kernels (rats, node IR) pair chains whose

@@ -16,7 +16,7 @@ using Mamba
 import Distributions
 import Distributions: Univariate, Multivariate
 import Mamba: Model, Sampler, ModelState, ModelChains, Chains, AMWGTune, AMMTune, NUTSTune,
-              SliceTune, HMCTune, MALATune, SamplerTune, relist!, unlist, gettune
+              SliceTune, HMCTune, MALATune, RWMTune, SamplerTune, relist!, unlist, gettune
 
 const libmambahip = "libmambahip"              # on LD_LIBRARY_PATH / DL_LOAD_PATH
 
@@ -25,6 +25,11 @@ const MMB_E_UNSUPPORTED = Int32(-2)
 const MMB_MODEL_LINE, MMB_MODEL_RATS, MMB_MODEL_LOGISTIC = Int32(1), Int32(2), Int32(3)
 const MMB_SAMPLER_AMWG, MMB_SAMPLER_AMM, MMB_SAMPLER_NUTS, MMB_SAMPLER_SLICE = Int32(1), Int32(2), Int32(3), Int32(4)
 const MMB_SAMPLER_GIBBS, MMB_SAMPLER_HMC, MMB_SAMPLER_MALA = Int32(5), Int32(6), Int32(7)
+const MMB_SAMPLER_RWM = Int32(8)
+# mmb_rwm_proposal: Normal and the SymDistributionTypes (src/distributions/extensions.jl:51-53)
+const MMB_RWM_PROPOSAL = Dict{Any,Int32}(Distributions.Normal => 0, Mamba.SymUniform => 1,
+                                         Mamba.SymTriangularDist => 2, Mamba.Epanechnikov => 3,
+                                         Mamba.Biweight => 4, Mamba.Triweight => 5, Mamba.Cosine => 6)
 const MMB_ADAPT = Dict(:all => Int32(0), :burnin => Int32(1), :none => Int32(2))
 const MMB_GRAD_DEFAULT, MMB_GRAD_FORWARD, MMB_GRAD_ANALYTIC = Int32(0), Int32(1), Int32(2)  # mmb_gradient
 # dtype of NUTS / HMC / MALA -> mmb_gradient.  :forward is the reference's default (Calculus,
@@ -327,11 +332,14 @@ MALA(params, epsilon::Real, pargs...; dtype::Symbol=:forward) =              # m
   register(Mamba.MALA(params, epsilon, pargs...; dtype=julia_dtype(dtype)), MMB_SAMPLER_MALA,
            (epsilon, pargs...), Any[(:dtype, dtype)])
 
+RWM(params, scale; proposal=Distributions.Normal) =                                      # rwm.jl:49-63
+  register(Mamba.RWM(params, scale; proposal=proposal), MMB_SAMPLER_RWM, (scale,), Any[(:proposal, proposal)])
+
 # tune type each constructor creates (amwg.jl:60, amm.jl:58, nuts.jl:55, slice.jl:57,
 # hmc.jl:64, mala.jl:59): a registered block must still carry it
 const TUNE_OF = Dict(MMB_SAMPLER_AMWG => AMWGTune, MMB_SAMPLER_AMM => AMMTune, MMB_SAMPLER_NUTS => NUTSTune,
                      MMB_SAMPLER_SLICE => SliceTune, MMB_SAMPLER_HMC => HMCTune, MMB_SAMPLER_MALA => MALATune,
-                     MMB_SAMPLER_GIBBS => GibbsTune)
+                     MMB_SAMPLER_GIBBS => GibbsTune, MMB_SAMPLER_RWM => RWMTune)
 
 # ---- model lowering --------------------------------------------------------------------------
 # Engine value layout per model kind (include/mamba_hip.h node ids; model.py offsets):
@@ -385,6 +393,13 @@ function block_spec(s::Sampler, nodes::NTuple{4,Int32}, nnodes::Integer, dim::In
     length(w) == dim || throw(ArgumentError("length(width) differs from variate length $dim"))
     form = r.pargs[2] == Univariate ? Int32(1) : Int32(0)
     return blk(MMB_ADAPT[:none], form, Int32(kwarg(r, :transform, false)), 0, 0.0, 0.0, 0.0, w, 0.0, 0)
+  elseif r.kind == MMB_SAMPLER_RWM                                             # rwm.jl:5-23, 39-44
+    isa(r.pargs[1], Real) || length(r.pargs[1]) == dim ||
+      throw(ArgumentError("length(scale) differs from variate length $dim"))
+    sc = fillvec(r.pargs[1], dim); push!(keep, sc)                             # the engine takes scale[dim]
+    form = get(MMB_RWM_PROPOSAL, kwarg(r, :proposal, Distributions.Normal), Int32(-1))
+    form < 0 && return nothing                      # a proposal the device does not draw: Julia path
+    return blk(MMB_ADAPT[:none], form, 1, 0, 0.0, 0.0, 0.0, sc, 0.0, 0)
   else                                                                         # hmc.jl:5-32, mala.jl:5-30
     grad < 0 && return nothing
     hmc = r.kind == MMB_SAMPLER_HMC
@@ -862,6 +877,9 @@ function pack_tune(t, s::Sampler, dim::Integer, iter::Integer)
     return Float64[t.epsilon, t.L]
   elseif isa(t, MALATune)
     return Float64[t.epsilon]
+  elseif isa(t, RWMTune)                            # scale[d]: the Sampler's RWMTune() is empty (rwm.jl:57-62
+    r = registered(s)                               # builds the variate's tune at every call), so the
+    return r === nothing ? Float64[] : fillvec(r.pargs[1], dim)   # row comes from the constructor's argument
   end
   Float64[]                                         # Slice, Gibbs: nothing is adapted
 end

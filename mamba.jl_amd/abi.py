@@ -14,6 +14,9 @@ MMB_MAX_NODES_PER_BLOCK = 4
 MMB_MODEL_LINE, MMB_MODEL_RATS, MMB_MODEL_LOGISTIC, MMB_MODEL_IR = 1, 2, 3, 4
 MMB_SAMPLER_AMWG, MMB_SAMPLER_AMM, MMB_SAMPLER_NUTS, MMB_SAMPLER_SLICE, MMB_SAMPLER_GIBBS = 1, 2, 3, 4, 5
 MMB_SAMPLER_HMC, MMB_SAMPLER_MALA = 6, 7
+MMB_SAMPLER_RWM = 8  # additive: MMB_ABI_VERSION is unchanged
+(MMB_RWM_NORMAL, MMB_RWM_SYMUNIFORM, MMB_RWM_SYMTRIANGULAR, MMB_RWM_EPANECHNIKOV, MMB_RWM_BIWEIGHT,
+ MMB_RWM_TRIWEIGHT, MMB_RWM_COSINE) = range(7)
 MMB_ABI_VERSION = 10
 MMB_GRAD_DEFAULT, MMB_GRAD_FORWARD, MMB_GRAD_ANALYTIC = 0, 1, 2
 MMB_SUMMARY_FIELDS, MMB_ORDER_MAX_TARGETS = 10, 16
@@ -141,6 +144,7 @@ def _declare(lib):
         "mmb_nuts_stats": (C.c_int, [P, C.POINTER(I64)]),
         "mmb_amm_stats": (C.c_int, [P, C.POINTER(I64)]),
         "mmb_amwg_stats": (C.c_int, [P, C.POINTER(I64)]),
+        "mmb_rwm_stats": (C.c_int, [P, C.POINTER(I64)]),
         "mmb_chain_order": (C.c_int, [P, C.POINTER(C.c_int32)]),
         "mmb_debug_pchol": (C.c_int, [C.c_int, I64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

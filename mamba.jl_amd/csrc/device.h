@@ -14,6 +14,7 @@
 
 #include "mamba_hip.h"
 #include "mmb_math.h"
+#include "symdist.h"
 #include "ir_math.h"
 
 #define MMB_MAXB MMB_MAX_BLOCKS
@@ -88,7 +89,7 @@ struct DBlock {
   const double* width;   // Slice: widths[d] (device) or null when scalar
   const double* sigl;    // AMM, HMC/MALA: chol(Sigma) lower, row-major d x d (device); HMC/MALA: null = I
   // tune state (device, chain-major)
-  double* t_sigma;       // AMWG  [K][DP]
+  double* t_sigma;       // AMWG  [K][DP]; RWM [K][DP] scale (RWMTune.scale)
   double* t_accept;      // AMWG  [K][DP]
   int32_t* t_m;          // AMWG/AMM/NUTS m [K]
   int32_t* t_flags;      // [K] bit0 adapt, bit1 AMM alias, bit2 AMM factor valid, bit3 NUTS init,
@@ -103,7 +104,8 @@ struct DBlock {
   double* t_xnext;       // AMM   [K][DP] next iteration's proposal minus v (samplers.h amm: formed
                          //       with the factor still in registers), valid when t_xtag[c] matches
   int64_t* t_xtag;       // AMM   [K] (xepoch << 32) | iteration the carried proposal is for
-  uint64_t* t_astat;     // AMM   [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats), diagnostics
+  uint64_t* t_astat;     // AMM   [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats), diagnostics;
+                         // RWM   the same rows: [0] updates, [1] accepts (mmb_rwm_stats)
   double* t_nuts;        // NUTS  [K][8] eps, epsbar, Hbar, mu, alpha, nalpha, -, -
   double* t_nfr;         // NUTS  [K][NutsFrames<DV>::DBL] tree frames (scratch, nuts.h)
   double* t_hmc;         // HMC/MALA [K][2] epsilon, L (HMCTune / MALATune, hmc.jl:5-28)

@@ -104,7 +104,8 @@ struct BlockHost {
   uint8_t* piv = nullptr;
   double* xnext = nullptr;   // AMM carried next proposal [K][DP] (samplers.h amm)
   int64_t* xtag = nullptr;   // AMM [K] tag of the carried proposal
-  uint64_t* astat = nullptr; // AMM [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats)
+  uint64_t* astat = nullptr; // AMM [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats);
+                             // RWM: the same rows, [0] updates, [1] accepts (mmb_rwm_stats)
   int32_t* sep_d = nullptr;  // node-IR AMWG: coordinate -> element-term table (ir_sep_table), engine lifetime
   double sep_eps = 0.0;
 };
@@ -320,6 +321,7 @@ static int tune_len_of(int kind, int d) {
     case MMB_SAMPLER_NUTS: return 9;
     case MMB_SAMPLER_HMC: return 2;   // [epsilon, L]     (HMCTune, hmc.jl:5-10)
     case MMB_SAMPLER_MALA: return 1;  // [epsilon]        (MALATune, mala.jl:5-9)
+    case MMB_SAMPLER_RWM: return d;   // scale[d]         (RWMTune, rwm.jl:5-9)
     default: return 0;
   }
 }
@@ -569,6 +571,21 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
             delete e;
             return fail(nullptr, MMB_E_ARG, "PosDefException: Sigma is not positive definite");
           }
+        }
+        break;
+      case MMB_SAMPLER_RWM:  // validate(v) (rwm.jl:39-44); the host broadcasts a scalar scale
+        if (s.dim != d || s.ntuning != d) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "length(scale) differs from variate length %d", d);
+        }
+        for (int i = 0; i < d; ++i)
+          if (!(std::isfinite(s.tuning[i]) && s.tuning[i] >= 0.0)) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: RWM scale[%d] must be finite and >= 0", b, i);
+          }
+        if (s.form < MMB_RWM_NORMAL || s.form > MMB_RWM_COSINE) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: unknown RWM proposal %d", b, s.form);
         }
         break;
       default:
@@ -1226,6 +1243,14 @@ int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_
       HIPCHK(e, hipMemset(h.astat, 0, K * MMB_AMM_STAT_STRIDE * sizeof(uint64_t)));
       HIPCHK(e, dalloc(&h.sigl_d, (size_t)h.d * h.d));
       HIPCHK(e, hipMemcpy(h.sigl_d, h.sigl.data(), h.sigl.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else if (h.spec.sampler == MMB_SAMPLER_RWM) {
+      HIPCHK(e, dalloc(&h.sigma, K * DP));
+      std::vector<double> sg(K * DP, 0.0);
+      for (int64_t k = 0; k < K; ++k)
+        for (int i = 0; i < h.d; ++i) sg[k * DP + i] = h.tuning[i];
+      HIPCHK(e, hipMemcpy(h.sigma, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(e, dalloc(&h.astat, K * MMB_AMM_STAT_STRIDE));
+      HIPCHK(e, hipMemset(h.astat, 0, K * MMB_AMM_STAT_STRIDE * sizeof(uint64_t)));
     } else if (h.spec.sampler == MMB_SAMPLER_NUTS) {
       HIPCHK(e, dalloc(&h.nuts, K * 8));
       HIPCHK(e, hipMemset(h.nuts, 0, K * 8 * sizeof(double)));
@@ -1997,6 +2022,11 @@ int mmb_get_tune(mmb_engine* e, double* tune) {
       if ((rc = d2h(e, th, h.hmc, K * 2))) return rc;
       for (int64_t k = 0; k < K; ++k)
         for (int i = 0; i < h.tune_len; ++i) tune[k * TL + off + i] = th[k * 2 + i];
+    } else if (h.spec.sampler == MMB_SAMPLER_RWM) {
+      std::vector<double> sg;
+      if ((rc = d2h(e, sg, h.sigma, K * DP))) return rc;
+      for (int64_t k = 0; k < K; ++k)
+        for (int i = 0; i < h.d; ++i) tune[k * TL + off + i] = sg[k * DP + i];
     }
     off += h.tune_len;
   }
@@ -2090,6 +2120,11 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
         th[k * 2 + 1] = h.tune_len > 1 ? t[1] : (double)h.spec.nsteps;
       }
       if ((rc = h2d(e, h.hmc, th))) return rc;
+    } else if (h.spec.sampler == MMB_SAMPLER_RWM) {
+      std::vector<double> sg(K * DP, 0.0);
+      for (int64_t k = 0; k < K; ++k)
+        for (int i = 0; i < h.d; ++i) sg[k * DP + i] = tune[k * TL + off + i];
+      if ((rc = h2d(e, h.sigma, sg))) return rc;
     }
     if ((rc = h2d(e, h.m, m)) || (rc = h2d(e, h.flags, fl))) return rc;
     off += h.tune_len;
@@ -2803,6 +2838,7 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
       case MMB_SAMPLER_NUTS: s += 8.0 * 7 + 4.0; break;
       case MMB_SAMPLER_HMC: s += 8.0 * 2; break;   // epsilon, L (read only)
       case MMB_SAMPLER_MALA: s += 8.0; break;
+      case MMB_SAMPLER_RWM: s += 8.0 * h.d; break;  // scale (read only)
       default: break;
     }
   }
@@ -2843,11 +2879,28 @@ int mmb_amm_stats(mmb_engine* e, int64_t* out) {
   HIPCHK(e, hipStreamSynchronize(e->stream));
   std::vector<uint64_t> h;
   for (size_t b = 0; b < e->blocks.size(); ++b) {
-    if (!e->blocks[b].astat) continue;
+    if (!e->blocks[b].astat || e->blocks[b].spec.sampler != MMB_SAMPLER_AMM) continue;
     int rc = d2h(e, h, e->blocks[b].astat, (size_t)e->K * MMB_AMM_STAT_STRIDE);
     if (rc) return rc;
     for (int64_t k = 0; k < e->K; ++k)
       for (int i = 0; i < MMB_AMM_STATS; ++i) out[b * MMB_AMM_STATS + i] += (int64_t)h[k * MMB_AMM_STAT_STRIDE + i];
+  }
+  return 0;
+}
+
+int mmb_rwm_stats(mmb_engine* e, int64_t* out) {
+  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
+  for (int i = 0; i < MMB_MAX_BLOCKS * 2; ++i) out[i] = 0;
+  if (e->K == 0) return 0;
+  HIPCHK(e, hipSetDevice(e->device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  std::vector<uint64_t> h;
+  for (size_t b = 0; b < e->blocks.size(); ++b) {
+    if (!e->blocks[b].astat || e->blocks[b].spec.sampler != MMB_SAMPLER_RWM) continue;
+    int rc = d2h(e, h, e->blocks[b].astat, (size_t)e->K * MMB_AMM_STAT_STRIDE);
+    if (rc) return rc;
+    for (int64_t k = 0; k < e->K; ++k)
+      for (int i = 0; i < 2; ++i) out[b * 2 + i] += (int64_t)h[k * MMB_AMM_STAT_STRIDE + i];
   }
   return 0;
 }

@@ -218,6 +218,48 @@ struct Smp {
     M::relist(B, s, g, x);
   }
 
+  // ---------------------------------------------------------------- RWM
+  // rwm.jl:65-71 (sample!): x = v + scale .* rand(proposal(0.0, 1.0), n), accepted iff
+  // rand() < exp(logpdf!(block, x) - logpdf!(block, v)); both log densities are evaluated at every
+  // update (the reference caches nothing) and nothing adapts.  v is unlisted with transform
+  // (rwm.jl:52).  A NaN ratio rejects and +inf accepts by the comparison itself.  Element e's
+  // variate is drawn by the lane that owns it: normal #e of the block's MMB_SUB_NORMAL stream, or
+  // symdist.h's variate of coordinate e on MMB_SUB_PROPOSAL; the accept uniform is #0 of
+  // MMB_SUB_UNIFORM.  Tune: scale[d] per chain (RWMTune.scale, B.t_sigma); the update and accept
+  // counts (mmb_rwm_stats) are added by lane 0 with no-return atomics, as amm_count's.
+  __device__ __forceinline__ static void rwm(const SweepArgs& A, const DBlock& B, int c, uint32_t chain, int64_t it,
+                                             int b, const mmb_rng& rn, const mmb_rng& ru, St& s, const Lc& l,
+                                             const Grp<G>& g, typename M::PrepCache& pk) {
+    const int d = B.d;
+    const mmb_rng rp = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_PROPOSAL);
+    double v[R], x[R];
+    M::unlist(B, s, g.lane, v);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int e = r * G + g.lane;
+      double sc = 0.0, z = 0.0;
+      if (e < d) {
+        sc = B.t_sigma[(size_t)c * DP + e];
+        z = B.form == MMB_RWM_NORMAL ? mmb_normal(&rn, (uint32_t)e) : mmb_symdist(B.form, &rp, (uint32_t)e);
+      }
+      x[r] = v[r] + sc * z;
+    }
+    const typename M::Prep pc = M::prep(B, s, g, pk);
+    double lx, lv;
+    M::logf_p2(A, B, pc, s, l, g, x, v, lx, lv);
+    const bool acc = mmb_uniform(&ru, 0u) < mmb_exp(lx - lv);
+    if (acc) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) v[r] = x[r];
+    }
+    if (g.lane == 0 && B.t_astat != nullptr) {
+      uint64_t* a = B.t_astat + (size_t)c * MMB_AMM_STAT_STRIDE;
+      (void)__hip_atomic_fetch_add(a + 0, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (acc) (void)__hip_atomic_fetch_add(a + 1, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    M::relist(B, s, g, v);
+  }
+
   // ---------------------------------------------------------------- pivoted Cholesky
   // cholfact(Hermitian(S), Val{true}) restated in LAPACK dpstf2('U', tol = 0) op order
   // (oracle.c orc_pchol): pivot = first maximum of the remaining diagonal in position

@@ -149,6 +149,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
         case MMB_SAMPLER_MALA:
           if constexpr ((KINDS >> MMB_SAMPLER_MALA) & 1u) S::template hmc<true>(A, B, c, rn, ru, s, g);
           break;
+        case MMB_SAMPLER_RWM:
+          if constexpr ((KINDS >> MMB_SAMPLER_RWM) & 1u) S::rwm(A, B, c, chain, it, b, rn, ru, s, l, g, pk);
+          break;
         case MMB_SAMPLER_GIBBS: if constexpr ((KINDS >> MMB_SAMPLER_GIBBS) & 1u) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
           const mmb_rng gu = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_U);
@@ -210,4 +213,7 @@ constexpr unsigned K_GIBBS_AMM = (1u << MMB_SAMPLER_AMM) | (1u << MMB_SAMPLER_GI
 constexpr unsigned K_SLICE_AMWG = (1u << MMB_SAMPLER_AMWG) | (1u << MMB_SAMPLER_SLICE);
 constexpr unsigned K_IR = (1u << MMB_SAMPLER_AMWG) | (1u << MMB_SAMPLER_AMM) | (1u << MMB_SAMPLER_SLICE) |
                          (1u << MMB_SAMPLER_GIBBS) | K_GRAD;
+// RWM is compiled only into kernels of their own, which schemes that hold an RWM block take
+// (sweep.hip): the instantiations above keep their masks, and so their code
+constexpr unsigned K_RWM = 1u << MMB_SAMPLER_RWM;
 

@@ -158,16 +158,24 @@ hipError_t mmb_launch_line_amm(const SweepArgs& A, hipStream_t st);  // line_amm
 hipError_t mmb_launch_sweep(int model, unsigned kinds, const SweepArgs& A, hipStream_t st) {
   if (model == MMB_MODEL_RATS) {
     constexpr int TB = MMB_RATS_BLOCK;
+    if (kinds & K_RWM) return launch<MMB_MODEL_RATS, K_ALL | K_RWM>(A, st, TB);
     if ((kinds & ~K_GIBBS_AMM) == 0) return launch<MMB_MODEL_RATS, K_GIBBS_AMM>(A, st, TB);
     if ((kinds & ~K_SLICE_AMWG) == 0) return launch<MMB_MODEL_RATS, K_SLICE_AMWG>(A, st, TB);
     return launch<MMB_MODEL_RATS, K_ALL>(A, st, TB);
   }
-  if (model == MMB_MODEL_IR) return launch<MMB_MODEL_IR, K_IR>(A, st, 128);
+  if (model == MMB_MODEL_IR) {
+    if (kinds & K_RWM) return launch<MMB_MODEL_IR, K_IR | K_RWM>(A, st, 128);
+    return launch<MMB_MODEL_IR, K_IR>(A, st, 128);
+  }
   if (model == MMB_MODEL_LINE) {
     // one AMM block (BASELINE configs[1]): four lanes per chain, tune state in registers
     // (line_amm.hip); bit-identical to the generic kernel, which MMB_LINE_GENERIC=1 selects
     if (kinds == (1u << MMB_SAMPLER_AMM) && A.nb == 1 && !std::getenv("MMB_LINE_GENERIC"))
       return mmb_launch_line_amm(A, st);
+    if (kinds & K_RWM) {
+      if (kinds & K_GRAD) return launch<MMB_MODEL_LINE, K_ALL_GRAD | K_RWM>(A, st, 64);
+      return launch<MMB_MODEL_LINE, K_ALL | K_RWM>(A, st, 64);
+    }
     if (kinds & K_GRAD) return launch<MMB_MODEL_LINE, K_ALL_GRAD>(A, st, 64);
     return launch<MMB_MODEL_LINE, K_ALL>(A, st, 64);
   }
@@ -178,10 +186,14 @@ hipError_t mmb_launch_sweep(int model, unsigned kinds, const SweepArgs& A, hipSt
 hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu) {
   if (model == MMB_MODEL_RATS) {
     constexpr int TB = MMB_RATS_BLOCK;
+    if (kinds & K_RWM) return shape<MMB_MODEL_RATS, K_ALL | K_RWM>(A, TB, nwg, wg_per_cu);
     if ((kinds & ~K_GIBBS_AMM) == 0) return shape<MMB_MODEL_RATS, K_GIBBS_AMM>(A, TB, nwg, wg_per_cu);
     if ((kinds & ~K_SLICE_AMWG) == 0) return shape<MMB_MODEL_RATS, K_SLICE_AMWG>(A, TB, nwg, wg_per_cu);
     return shape<MMB_MODEL_RATS, K_ALL>(A, TB, nwg, wg_per_cu);
   }
-  if (model == MMB_MODEL_IR) return shape<MMB_MODEL_IR, K_IR>(A, 128, nwg, wg_per_cu);
+  if (model == MMB_MODEL_IR) {
+    if (kinds & K_RWM) return shape<MMB_MODEL_IR, K_IR | K_RWM>(A, 128, nwg, wg_per_cu);
+    return shape<MMB_MODEL_IR, K_IR>(A, 128, nwg, wg_per_cu);
+  }
   return hipErrorInvalidValue;
 }

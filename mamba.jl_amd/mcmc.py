@@ -157,6 +157,20 @@ class Engine:
             out[b] = {"updates": r[0], "full_rank": r[1], "rank_sum": r[2], "steps_sum": r[3], "redo": r[4]}
         return out
 
+    def rwm_stats(self):
+        """RWM counters since init_chains (mmb_rwm_stats), one dict per RWM block (keyed by block
+        index), summed over the chains: block updates and accepted ones (rwm.jl:67-70).  RWM does
+        not adapt: size `scale` from this acceptance rate."""
+        v = (C.c_int64 * (abi.MMB_MAX_BLOCKS * 2))()
+        self._chk(self.lib.mmb_rwm_stats(self.h, v))
+        out = {}
+        for b, blk in enumerate(self.model.samplers):
+            if getattr(blk, "kind", None) != abi.MMB_SAMPLER_RWM:
+                continue
+            out[b] = {"updates": v[2 * b], "accepts": v[2 * b + 1],
+                      "rate": v[2 * b + 1] / v[2 * b] if v[2 * b] else float("nan")}
+        return out
+
     def amwg_stats(self):
         """AMWG block updates since init_chains that ran the sequential coordinate loop
         (mmb_amwg_stats) rather than the lane-parallel decision of every coordinate."""

@@ -112,7 +112,7 @@ class Model:
             bs.dim = self.block_dim(s)
             bs.epsilon, bs.nsteps, bs.gradient = s.epsilon, s.nsteps, s.gradient
             if s.tuning is not None:
-                t = np.ascontiguousarray(s.tuning, dtype=np.float64)
+                t = np.ascontiguousarray(s.spec_tuning(bs.dim), dtype=np.float64)
                 keep.append(t)
                 bs.ntuning = t.size
                 bs.tuning = abi.dptr(t)

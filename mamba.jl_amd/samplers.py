@@ -10,6 +10,7 @@ Argument meaning, defaults and validation errors follow the reference:
   Slice(params, width, Univariate|Multivariate; transform=false) src/samplers/slice.jl:47-58
   HMC(params, epsilon, L[, Sigma]; dtype=:forward)            src/samplers/hmc.jl:47-65
   MALA(params, epsilon[, Sigma]; dtype=:forward)              src/samplers/mala.jl:43-58
+  RWM(params, scale, proposal=Normal)                          src/samplers/rwm.jl:49-63
   Gibbs(params)  -- a user `Sampler(params, f)` whose f is the node's conjugate full
                     conditional (doc/tutorial/line.jl:27-45); lowered per model.
 """
@@ -19,6 +20,13 @@ from . import abi
 
 Univariate = "Univariate"
 Multivariate = "Multivariate"
+
+# RWM proposals: Normal and the SymDistributionTypes (src/distributions/extensions.jl:51-53)
+Normal, SymUniform, SymTriangularDist = "Normal", "SymUniform", "SymTriangularDist"
+Epanechnikov, Biweight, Triweight, Cosine = "Epanechnikov", "Biweight", "Triweight", "Cosine"
+RWM_PROPOSALS = {Normal: abi.MMB_RWM_NORMAL, SymUniform: abi.MMB_RWM_SYMUNIFORM,
+                 SymTriangularDist: abi.MMB_RWM_SYMTRIANGULAR, Epanechnikov: abi.MMB_RWM_EPANECHNIKOV,
+                 Biweight: abi.MMB_RWM_BIWEIGHT, Triweight: abi.MMB_RWM_TRIWEIGHT, Cosine: abi.MMB_RWM_COSINE}
 
 
 class ArgumentError(ValueError):
@@ -68,9 +76,18 @@ class Sampler:
             raise ArgumentError(f"length(width) differs from variate length {dim}")
         if self.kind in (abi.MMB_SAMPLER_HMC, abi.MMB_SAMPLER_MALA) and t is not None and t.size != dim * dim:
             raise ArgumentError(f"Sigma dimension differs from variate length {dim}")
+        if self.kind == abi.MMB_SAMPLER_RWM and not (t.size == 1 or t.size == dim):  # rwm.jl:39-44
+            raise ArgumentError(f"length(scale) differs from variate length {dim}")
+
+    def spec_tuning(self, dim):
+        """`tuning` as the block spec carries it: RWM's scalar scale is broadcast to the variate length
+        (the engine takes scale[dim]); every other kind passes its vector as it is."""
+        if self.kind == abi.MMB_SAMPLER_RWM and self.tuning.size == 1:
+            return np.full(dim, self.tuning[0])
+        return self.tuning
 
     def __repr__(self):
-        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA"}
+        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM"}
         return f"{names[self.kind]}({self.params})"
 
 
@@ -141,6 +158,19 @@ def Slice(params, width, form=Multivariate, transform=False):
         raise ArgumentError("form must be Univariate or Multivariate")
     return Sampler(params, abi.MMB_SAMPLER_SLICE, abi.MMB_ADAPT_NONE, width, form=f,
                    transform=transform)
+
+
+def RWM(params, scale, proposal=Normal):
+    """RWM(params, scale; proposal=Normal) -- rwm.jl:49-63; tune scale[d] (RWMTune), no adaptation.
+    `proposal`: Normal or a SymDistributionType name, in any letter case."""
+    names = {k.lower(): v for k, v in RWM_PROPOSALS.items()}
+    form = names.get(str(proposal).lstrip(":").lower())
+    if form is None:
+        raise ArgumentError(f"unsupported proposal {proposal}: one of {', '.join(RWM_PROPOSALS)}")
+    sc = np.atleast_1d(np.asarray(scale, dtype=np.float64))
+    if sc.ndim != 1 or not (np.isfinite(sc).all() and (sc >= 0.0).all()):
+        raise ArgumentError("scale must be a finite non-negative scalar or vector")
+    return Sampler(params, abi.MMB_SAMPLER_RWM, abi.MMB_ADAPT_NONE, sc, form=form, transform=True)
 
 
 def Gibbs(params):

@@ -42,6 +42,8 @@ def models():
                    mb.AMWG("s2", 0.1)])
     m.init_matrix([ir.seeds_inits()[k % 2] for k in range(2)], 2)
     out.append(("seeds_ir_bench", m))
+    import test_gpu_rwm as R
+    out += R.ir_models()
     return out
 
 
