@@ -5,7 +5,10 @@
  * §2), the transform rules of src/distributions/transformdistribution.jl:6-93, the unary
  * operators of the expression code (Mamba's invlogit/logit, src/utils.jl:64-68) and lgamma.
  * Pinned independently: element densities against scipy.stats and lgamma against libm
- * (tests/test_ir.py).
+ * (tests/test_ir.py), and both against 50-digit references at and around every support
+ * boundary (tests/ir_family_ref.py; on the device by tests/test_gpu_ir_families.py).
+ * At a boundary a density is its limit there, never NaN: a NaN log density passes a Slice shrink
+ * test !(lp < p0) as an improvement.
  */
 #ifndef MMB_IR_MATH_H
 #define MMB_IR_MATH_H
@@ -88,6 +91,12 @@ MMB_HD double mmb_ir_normal_lb(double x, double a, double b, double lb) {
   return -(z * z + MMB_LOG2PI) / 2.0 - lb;
 }
 
+/* c log x with xlogy's convention 0 log 0 = 0 (lx = mmb_log(x)): a Beta(1, b) or Gamma(1, theta)
+ * density is finite at the boundary x = 0, where c * lx would be 0 * -Inf = NaN -- which the Slice
+ * shrink test !(lp < p0) takes for a point inside the slice.  Every other (c, x) is the plain
+ * product, so interior values keep their bits. */
+MMB_HD double mmb_ir_xlogy(double c, double x, double lx) { return (c == 0.0 && x == 0.0) ? 0.0 : c * lx; }
+
 MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr, double lo, double hi) {
   const double NINF = -__builtin_inf(), INF = __builtin_inf();
   switch (fam) {
@@ -97,19 +106,20 @@ MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr
       return -(z * z + MMB_LOG2PI) / 2.0 - mmb_log(b);
     }
     case MMB_IR_INVGAMMA: { /* a log b - lgamma(a) - (a + 1) log x - b / x */
-      if (!(0.0 <= x && x <= INF)) return NINF;
+      if (!(0.0 < x && x < INF)) return NINF; /* the density's limit at both ends of the support is 0 */
       const double lx = mmb_log(x);
       const double lp = a * mmb_log(b) - mmb_lgamma(a) - (a + 1.0) * lx - b / x;
       return tr ? lp + lx : lp;
     }
     case MMB_IR_GAMMA: { /* -lgamma(k) - k log theta + (k - 1) log x - x / theta */
-      if (!(0.0 <= x && x <= INF)) return NINF;
+      if (!(0.0 <= x && x < INF)) return NINF; /* x = Inf: the density's limit is 0 */
+      if (tr && x == 0.0) return NINF;         /* x f(x) ~ x^k -> 0, also where f(0) = +Inf (k < 1) */
       const double lx = mmb_log(x);
-      const double lp = -mmb_lgamma(a) - a * mmb_log(b) + (a - 1.0) * lx - x / b;
+      const double lp = -mmb_lgamma(a) - a * mmb_log(b) + mmb_ir_xlogy(a - 1.0, x, lx) - x / b;
       return tr ? lp + lx : lp;
     }
     case MMB_IR_EXPONENTIAL: { /* -log theta - x / theta */
-      if (!(0.0 <= x && x <= INF)) return NINF;
+      if (!(0.0 <= x && x < INF)) return NINF; /* x = Inf: the density's limit is 0 */
       const double lp = -mmb_log(a) - x / a;
       return tr ? lp + mmb_log(x) : lp;
     }
@@ -120,8 +130,10 @@ MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr
     }
     case MMB_IR_BETA: { /* (a-1) log x + (b-1) log(1-x) - lbeta(a, b); Jacobian log(x(1-x)) */
       if (!(0.0 <= x && x <= 1.0)) return NINF;
+      if (tr && (x == 0.0 || x == 1.0)) return NINF; /* x(1-x) f(x) -> 0, also where f = +Inf (a or b < 1) */
       const double lb = mmb_lgamma(a) + mmb_lgamma(b) - mmb_lgamma(a + b);
-      const double lp = (a - 1.0) * mmb_log(x) + (b - 1.0) * mmb_log(1.0 - x) - lb;
+      const double y = 1.0 - x;
+      const double lp = mmb_ir_xlogy(a - 1.0, x, mmb_log(x)) + mmb_ir_xlogy(b - 1.0, y, mmb_log(y)) - lb;
       return tr ? lp + mmb_log(x * (1.0 - x)) : lp;
     }
     case MMB_IR_BINOMIAL: { /* lchoose(n, k) + xlogy(k, p) + xlog1py(n - k, -p) */
@@ -130,6 +142,7 @@ MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr
       return ct + t1 + t2;
     }
     case MMB_IR_POISSON: { /* xlogy(k, lambda) - lambda - lgamma(k + 1) */
+      if (a == INF) return NINF; /* the limit; k log(Inf) - Inf is NaN (a rate expression can overflow) */
       const double t1 = x == 0.0 ? 0.0 : x * mmb_log(a);
       return ct + t1 - a;
     }

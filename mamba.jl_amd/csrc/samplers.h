@@ -7,6 +7,21 @@
 #include "hmc.h"
 #include "nuts.h"
 
+// Whether model M evaluates logpdf! in the chain state itself (Mdl<MMB_MODEL_IR>::NOPROP in the
+// specialised AMM / Gibbs kernels); false for models without the member.  amm() keeps a copy of
+// the old value only for these: the copy would serve every model (same products), but the line
+// and rats kernels are tuned to their register budgets, and with the split their instruction
+// streams are the ones they had (compared function by function in the device assembly of
+// sweep.hip) -- the simpler form's register cost in them has not been measured.
+template <class M, class = void>
+struct mmb_noprop {
+  static constexpr bool value = false;
+};
+template <class M>
+struct mmb_noprop<M, decltype((void)M::NOPROP)> {
+  static constexpr bool value = M::NOPROP;
+};
+
 template <class M>
 struct Smp {
   static constexpr int G = M::G, R = M::R, DMAX = M::DMAX, DP = M::DP, TP = M::TP;
@@ -993,6 +1008,13 @@ struct Smp {
       m += 1;
       const double p = (double)m / ((double)m + 1.0);
       const double q = 1.0 - p;
+      // fresh, models that evaluate logpdf! in the state itself (mmb_noprop): mv is still setadapt!'s
+      // copy of the unlisted old value, kept for Mvv = v_old v_old' below
+      double vkeep[R];
+      if constexpr (mmb_noprop<M>::value) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) vkeep[r] = mv[r];
+      }
       if (fl & 2) {
 #pragma unroll
         for (int r = 0; r < R; ++r) mv[r] = p * v[r] + q * v[r];
@@ -1014,10 +1036,17 @@ struct Smp {
       double* Mvv = ((dual && ((m - 1) & 1)) ? B.t_Mvv_alt : B.t_Mvv) + (size_t)c * TP;
       double* Mvv_w = ((dual && (m & 1)) ? B.t_Mvv_alt : B.t_Mvv) + (size_t)c * TP;
       // fresh: Mvv = v_old v_old' was formed before the proposal; v_old is still unlist()
-      // of the state `s`, so recompute it from s here (same products).
+      // of the state `s`, so recompute it from s here (same products).  Not so where logf_p2 has
+      // written invlink(v_old) into the state itself (the node IR's NOPROP layout): under a log or
+      // logit link unlist() of that is link(invlink(link(state))), a rounding away from v_old.
       double vold[R];
       if (fresh) {
-        M::unlist(B, s, g.lane, vold);
+        if constexpr (mmb_noprop<M>::value) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) vold[r] = vkeep[r];
+        } else {
+          M::unlist(B, s, g.lane, vold);
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           int e = r * G + g.lane;

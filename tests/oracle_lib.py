@@ -72,7 +72,20 @@ class Oracle:
         ns = (C.c_int64 * len(arrs))(*[a.size for a in arrs])
         return arrs, ptrs, ns
 
+    def _restated(self, model):
+        """oracle.c's run_chain restates these sampler kinds and skips any other block without a
+        word (RWM: tests/rwm_ref.py restates it): a run with one would be a comparison with chains
+        that never moved in that block."""
+        a = self.abi
+        known = {a.MMB_SAMPLER_AMWG, a.MMB_SAMPLER_AMM, a.MMB_SAMPLER_SLICE, a.MMB_SAMPLER_NUTS, a.MMB_SAMPLER_HMC,
+                 a.MMB_SAMPLER_MALA, a.MMB_SAMPLER_GIBBS}
+        for b, s in enumerate(model.samplers):
+            if s.kind not in known:
+                raise NotImplementedError(f"the oracle does not restate block {b}'s sampler (kind {s.kind}, "
+                                          f"{type(s).__name__})")
+
     def new_state(self, model, init):
+        self._restated(model)
         self._ir(model)
         spec = model.spec()
         arrs, ptrs, ns = self._data(model)
@@ -88,6 +101,7 @@ class Oracle:
 
     def run(self, model, state, iters, burnin=0, thin=1, model_burnin=None, chain_offset=0, seed=1,
             nthreads=1, draws=True):
+        self._restated(model)
         self._ir(model)
         spec = model.spec()
         arrs, ptrs, ns = self._data(model)

@@ -12,7 +12,9 @@ block b, chain c (global id), iteration it:
 The two log densities are the oracle's block_logpdf on a TWIN model -- the same model with every
 RWM block replaced by AMWG(params, 1.0), which has the same term list and transform = true -- so
 they are the oracle's own bits, which the AMWG parity tests assert are the kernels' bits.  Links
-are restated for identity and log nodes (orc_log / orc_exp); a logit-linked node raises.
+are restated from csrc/ir_math.h on orc_log / orc_exp and IEEE operations: identity, log
+(positive nodes), logit (Beta: log(x / (1 - x)), 1 / (exp(-y) + 1)) and affine logit (Uniform(lo, hi):
+logit((x - lo) / (hi - lo)), (hi - lo) invlogit(y) + lo).
 """
 import ctypes as C
 
@@ -66,6 +68,33 @@ def cdf(kind, z):
     raise ValueError(kind)
 
 
+def link(L, kind, x, lo, hi):
+    """mmb_ir_link restated (kind 0 identity, 1 log, 2 logit, 3 affine logit)."""
+    x, lo, hi = np.float64(x), np.float64(lo), np.float64(hi)
+    with np.errstate(all="ignore"):
+        if kind == 1:
+            return L.orc_log(x)
+        if kind == 2:
+            return L.orc_log(x / (np.float64(1.0) - x))
+        if kind == 3:
+            t = (x - lo) / (hi - lo)
+            return L.orc_log(t / (np.float64(1.0) - t))
+    return float(x)
+
+
+def invlink(L, kind, y, lo, hi):
+    """mmb_ir_invlink restated."""
+    lo, hi = np.float64(lo), np.float64(hi)
+    with np.errstate(all="ignore"):
+        if kind == 1:
+            return L.orc_exp(y)
+        if kind == 2:
+            return float(np.float64(1.0) / (np.float64(L.orc_exp(-y)) + np.float64(1.0)))
+        if kind == 3:
+            return float((hi - lo) * (np.float64(1.0) / (np.float64(L.orc_exp(-y)) + np.float64(1.0))) + lo)
+    return float(y)
+
+
 def twin_scheme(mb, scheme):
     """The scheme with each RWM block replaced by AMWG(params, 1.0)."""
     return [mb.AMWG(list(s.params), 1.0) if s.kind == mb.abi.MMB_SAMPLER_RWM else s for s in scheme]
@@ -83,17 +112,23 @@ class Restatement:
         self.arrs, self.ptrs, self.ns = oracle._data(twin)
         self.oracle = oracle
         self.blocks = []
+        a = mb.abi
         for b, s in enumerate(model.samplers):
-            idx, pos = [], []
+            idx, pos = [], []          # pos: per element (link kind, lo, hi)
             for p in s.params:
                 n = model.nodes[p]
                 tr = getattr(model, "traced", None)
                 fam = tr[p].fam if tr is not None and p in tr else None
-                if fam in (mb.abi.MMB_IR_UNIFORM, mb.abi.MMB_IR_BETA):
-                    raise NotImplementedError(f"logit-linked node {p}: the restatement covers identity and log links")
+                lk = (1 if n.positive else 0, 0.0, 0.0)
+                if fam == a.MMB_IR_BETA:
+                    lk = (2, 0.0, 0.0)
+                elif fam == a.MMB_IR_UNIFORM:
+                    N = model.ir().nodes[n.id]     # the node named p: its id, checked against its layout
+                    assert (N.family, N.off, N.len, N.fixed) == (fam, n.offset, n.dim, 0), p
+                    lk = (3, float(N.lo), float(N.hi))
                 idx += list(range(n.offset, n.offset + n.dim))
-                pos += [bool(n.positive)] * n.dim
-            self.blocks.append((s, np.array(idx), np.array(pos)))
+                pos += [lk] * n.dim
+            self.blocks.append((s, np.array(idx), pos))
         self.updates = {b: 0 for b, s in enumerate(model.samplers) if s.kind == mb.abi.MMB_SAMPLER_RWM}
         self.accepts = dict(self.updates)
         self.chain_accepts = {}  # (block, chain) -> accepted updates
@@ -116,7 +151,7 @@ class Restatement:
         """One RWM update of block b on the value row (in place).  Returns whether it accepted."""
         s, idx, pos = self.blocks[b]
         L, d = self.L, len(idx)
-        v = np.array([L.orc_log(row[i]) if p else row[i] for i, p in zip(idx, pos)])
+        v = np.array([link(L, p[0], row[i], p[1], p[2]) for i, p in zip(idx, pos)])
         g = self.off + chain
         x = np.empty(d)
         for k in range(d):
@@ -132,7 +167,7 @@ class Restatement:
         if acc:
             v = x
         for q, (i, p) in enumerate(zip(idx, pos)):
-            row[i] = L.orc_exp(v[q]) if p else v[q]
+            row[i] = invlink(L, p[0], v[q], p[1], p[2])
         return acc
 
     def monitored(self, row):

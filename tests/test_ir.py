@@ -84,6 +84,16 @@ ZOO_DATA = {"nn": [10.0, 12, 7, 20], "t": [1.0, 2.5, 0.5, 4.0, 1.5]}
 ZOO_FIXED = {"obs_bin": [3.0, 0, 7, 11], "obs_poi": [0.0, 4, 1, 9, 2], "obs_ber": [1.0, 0, 1]}
 
 
+def zoo_inits(rng, K):
+    """Initial values of K zoo chains, every node inside its support."""
+    inits = []
+    for k in range(K):
+        inits.append({**ZOO_FIXED, "p": rng.uniform(0.05, 0.95, 4), "lam": rng.gamma(2.0, 1.0, 5),
+                      "g": rng.gamma(2.0, 1.0), "th": rng.gamma(2.0, 1.0), "a": rng.uniform(0.6, 3.9),
+                      "b": rng.normal(3, 1), "m0": rng.normal(3, 1)})
+    return inits
+
+
 def zoo_ref_lp(blockparams, v, transform):
     """logpdf!(m, x, block, transform) by scipy: params \\ targets, then targets."""
     p, lam, g, th, a, b, m0 = v["p"], v["lam"], v["g"], v["th"], v["a"], v["b"], v["m0"]
@@ -121,11 +131,7 @@ def test_ir_families_vs_scipy(mamba, oracle):
                mamba.Slice(["b", "m0"], 1.0), mamba.NUTS(["g", "th", "lam"])]
     m.setsamplers(schemes)
     rng = np.random.default_rng(7)
-    inits = []
-    for k in range(6):
-        inits.append({**ZOO_FIXED, "p": rng.uniform(0.05, 0.95, 4), "lam": rng.gamma(2.0, 1.0, 5),
-                      "g": rng.gamma(2.0, 1.0), "th": rng.gamma(2.0, 1.0), "a": rng.uniform(0.6, 3.9),
-                      "b": rng.normal(3, 1), "m0": rng.normal(3, 1)})
+    inits = zoo_inits(rng, 6)
     V = m.init_matrix(inits, 6)
     names = ["p", "lam", "g", "th", "a", "b", "m0"]
     off = {n: m.nodes[n].offset for n in names}
@@ -382,3 +388,230 @@ def test_ir_gibbs_closure_line_s2(mamba, oracle):
     sth = oracle.new_state(h, init)
     dh = oracle.run(h, sth, 200, burnin=100, thin=1, seed=9, nthreads=8)
     np.testing.assert_allclose(d, dh, rtol=1e-9, atol=1e-12)
+
+
+# ---- the element layer (csrc/ir_math.h, as the oracle compiles it) against 50-digit references --------
+def _fam_ids(mamba):
+    a = mamba.abi
+    return {"normal": a.MMB_IR_NORMAL, "invgamma": a.MMB_IR_INVGAMMA, "gamma": a.MMB_IR_GAMMA,
+            "exponential": a.MMB_IR_EXPONENTIAL, "uniform": a.MMB_IR_UNIFORM, "beta": a.MMB_IR_BETA,
+            "binomial": a.MMB_IR_BINOMIAL, "poisson": a.MMB_IR_POISSON, "bernoulli": a.MMB_IR_BERNOULLI}
+
+
+def _elem(oracle, fid, x, a=None, b=None, ct=0.0, tr=False, lo=0.0, hi=0.0):
+    return oracle.L.orc_ir_elem_lp(fid, x, 0.0 if a is None else a, 0.0 if b is None else b, ct, int(tr), lo, hi)
+
+
+def binom_ct(n, k):
+    """The host-computed constant of a Binomial observation, as ir.py's lowering forms it."""
+    return math.lgamma(n + 1) - math.lgamma(k + 1) - math.lgamma(n - k + 1)
+
+
+def test_family_ref_vs_scipy():
+    """tests/ir_family_ref.py (mpmath, 50 digits) against scipy.stats at interior points of all ten
+    families, with and without the Jacobian.  Bound: 1e-13 M -- scipy evaluates the same sums of
+    at most six terms in doubles from gammaln / xlogy / log1p, each good to a few ulps of its own
+    term, so ~1e3 ulps (2^-53) of the term scale M is scipy's accuracy with room to spare, and
+    four orders tighter than what the kernels are held to."""
+    import ir_family_ref as R
+    rng = np.random.default_rng(11)
+    worst = 0.0
+
+    def cmp(got, want):
+        nonlocal worst
+        v, M = got
+        err = abs(float(v - R.mp.mpf(float(want))))
+        worst = max(worst, err / M)
+        assert err <= 1e-13 * M, (float(v), want, err, M)
+
+    for _ in range(40):
+        a, b = float(rng.gamma(2.0, 1.5)), float(rng.gamma(2.0, 1.5))
+        x = float(rng.gamma(2.0, 1.0))
+        u = float(rng.uniform(0.01, 0.99))
+        z, mu = float(rng.normal(0, 3)), float(rng.normal(0, 2))
+        for tr in (False, True):
+            j = math.log(x) if tr else 0.0
+            cmp(R.logpdf("gamma", x, a, b, tr), stats.gamma.logpdf(x, a, scale=b) + j)
+            cmp(R.logpdf("invgamma", x, a, b, tr), stats.invgamma.logpdf(x, a, scale=b) + j)
+            cmp(R.logpdf("exponential", x, a, tr=tr), stats.expon.logpdf(x, scale=a) + j)
+            cmp(R.logpdf("beta", u, a, b, tr), stats.beta.logpdf(u, a, b) + (math.log(u * (1 - u)) if tr else 0.0))
+            w = 0.5 + 3.5 * u
+            cmp(R.logpdf("uniform", w, tr=tr, lo=0.5, hi=4.0),
+                stats.uniform.logpdf(w, 0.5, 3.5) + (math.log((w - 0.5) * (4.0 - w) / 3.5) if tr else 0.0))
+            cmp(R.logpdf("normal", z, mu, b, tr), stats.norm.logpdf(z, mu, b))
+        n = int(rng.integers(1, 40))
+        k = int(rng.integers(0, n + 1))
+        cmp(R.logpdf("binomial", k, n, u), stats.binom.logpmf(k, n, u))
+        cmp(R.logpdf("poisson", k, x), stats.poisson.logpmf(k, x))
+        cmp(R.logpdf("bernoulli", k % 2, u), stats.bernoulli.logpmf(k % 2, u))
+        xs, ms = rng.normal(0, 2, 5), rng.normal(0, 2, 5)
+        cmp(R.logpdf("mvnormal", xs, ms, b), stats.norm.logpdf(xs, ms, b).sum())
+    print("worst |ref - scipy| / M =", worst)
+    # the support rule and the boundary conventions
+    assert R.logpdf("gamma", -1.0, 2.0, 1.0)[0] == R.NINF and R.logpdf("beta", float("nan"), 2.0, 1.0)[0] == R.NINF
+    assert R.logpdf("gamma", 0.0, 1.0, 2.0)[0] == -R.mp.log(2) and R.logpdf("gamma", 0.0, 0.5, 2.0)[0] == R.INF
+    assert R.logpdf("gamma", 0.0, 1.0, 2.0, True)[0] == R.NINF
+    assert R.mp.isnan(R.logpdf("gamma", 0.0, 0.5, 2.0, True)[0])
+
+
+# worst |mmb_lgamma - mpmath.loggamma| / (|(z - 1/2) log z| + z) over test_lgamma_vs_mpmath's grid outside
+# [1e-3, 1e4], measured on the oracle build: 6.58e-16 (three ulps of the Stirling terms' size)
+LGAMMA_MEASURED = 6.6e-16
+
+
+def test_lgamma_vs_mpmath(oracle):
+    """mmb_lgamma (the oracle's build of ir_math.h) against mpmath.loggamma over
+    geomspace(1e-300, 1e300) and around 1, 2 and 10.  On [1e-3, 1e4] the bound of
+    test_lgamma_vs_libm (rel 1e-14, abs 1e-14) holds against the 50-digit value too.  Outside,
+    the error is taken relative to M = |(z - 1/2) log z| + z: the worst over this grid measured
+    6.58e-16 (LGAMMA_MEASURED); 4x that, 2.64e-15 M, is asserted."""
+    import ir_family_ref as R
+    xs = np.concatenate([np.geomspace(1e-300, 1e300, 2401), np.geomspace(1e-3, 1e4, 400),
+                         [0.5, 1.0, 1.5, 2.0, 2.5, 9.999, 10.0, 10.001]])
+    worst_out = 0.0
+    for x in xs:
+        x = float(x)
+        got = oracle.L.orc_lgamma(x)
+        want = R.mp.loggamma(R.mp.mpf(x))
+        if 1e-3 <= x <= 1e4:
+            assert got == pytest.approx(float(want), rel=1e-14, abs=1e-14), x
+        else:
+            e = float(abs(R.mp.mpf(got) - want)) / float(R.lgamma_scale(x))
+            worst_out = max(worst_out, e)
+            assert e <= 4 * LGAMMA_MEASURED, (x, got, float(want), e)
+    print("worst |lgamma - mpmath| / M outside [1e-3, 1e4] =", worst_out)
+    assert oracle.L.orc_lgamma(0.0) == math.inf and math.isnan(oracle.L.orc_lgamma(-1.0))
+
+
+def test_ir_elem_edges_vs_ref(mamba, oracle):
+    """Every point of the edge grid (ir_family_ref.edge_grid, PROBS, RATES), with and without the
+    transform, on the oracle's element layer: the class (nan / +inf / -inf / finite) is the
+    reference's and finite values lie within 1e-12 M + 1e-13 -- the assertion the device test
+    (test_gpu_ir_families.py) makes of modelstats.hip at the same points."""
+    import ir_family_ref as R
+    F = _fam_ids(mamba)
+    n = 0
+    for fam in ("beta", "gamma", "invgamma", "exponential", "normal", "uniform"):
+        lo, hi = (R.UNIFORM_LO, R.UNIFORM_HI) if fam == "uniform" else (0.0, 0.0)
+        for x, a, b in R.edge_grid(fam):
+            for tr in (False, True):
+                got = _elem(oracle, F[fam], x, a, b, tr=tr, lo=lo, hi=hi)
+                R.check(got, *R.logpdf(fam, x, a, b, tr, lo, hi), where=(fam, x, a, b, tr), tr=tr)
+                n += 1
+    for k, nn in ((3.0, 10.0), (0.0, 12.0), (7.0, 7.0), (11.0, 20.0)):
+        for p in R.PROBS:
+            got = _elem(oracle, F["binomial"], k, nn, p, ct=binom_ct(nn, k))
+            R.check(got, *R.logpdf("binomial", k, nn, p), where=("binomial", k, nn, p))
+    for k in (0.0, 4.0, 9.0):
+        for lam in R.RATES:
+            for t in (1.0, 2.5):
+                got = _elem(oracle, F["poisson"], k, lam * t, ct=-math.lgamma(k + 1))
+                R.check(got, *R.logpdf("poisson", k, lam * t), where=("poisson", k, lam * t))
+    for x in (0.0, 1.0):
+        for p in R.PROBS:
+            R.check(_elem(oracle, F["bernoulli"], x, p), *R.logpdf("bernoulli", x, p), where=("bernoulli", x, p))
+    assert n > 1400
+
+
+def test_ir_boundary_values(mamba, oracle):
+    """The densities at the support boundaries, where (a - 1) log x is 0 * -Inf: Beta at 0 (+Inf,
+    log b, -Inf for a below, equal to and above 1), mirrored at 1, Gamma at 0 (+Inf, -log theta,
+    -Inf); InverseGamma at 0; with the transform -Inf everywhere the density is not +Inf (and
+    never NaN: a Slice shrink test !(lp < p0) accepts NaN)."""
+    F = _fam_ids(mamba)
+    e = lambda *a, **k: _elem(oracle, *a, **k)      # noqa: E731
+    inf = math.inf
+    # Beta(a, 3) at 0 and Beta(3, b) at 1
+    assert e(F["beta"], 0.0, 0.5, 3.0) == inf and e(F["beta"], 0.0, 2.0, 3.0) == -inf
+    assert e(F["beta"], 0.0, 1.0, 3.0) == pytest.approx(math.log(3.0), abs=1e-14)
+    assert e(F["beta"], 1.0, 3.0, 0.5) == inf and e(F["beta"], 1.0, 3.0, 2.0) == -inf
+    assert e(F["beta"], 1.0, 3.0, 1.0) == pytest.approx(math.log(3.0), abs=1e-14)
+    assert e(F["beta"], 0.0, 1.0, 1.0) == pytest.approx(0.0, abs=1e-14)
+    assert e(F["beta"], 1.0, 1.0, 1.0) == pytest.approx(0.0, abs=1e-14)
+    # Gamma(k, 2) at 0
+    assert e(F["gamma"], 0.0, 0.5, 2.0) == inf and e(F["gamma"], 0.0, 2.0, 2.0) == -inf
+    assert e(F["gamma"], 0.0, 1.0, 2.0) == pytest.approx(-math.log(2.0), abs=1e-14)
+    assert e(F["invgamma"], 0.0, 3.0, 2.0) == -inf
+    for fam, x, a, b in (("beta", 0.0, 1.0, 1.0), ("beta", 1.0, 1.0, 1.0), ("beta", 0.0, 0.5, 3.0),
+                         ("beta", 1.0, 3.0, 0.5), ("beta", 0.0, 2.0, 3.0), ("gamma", 0.0, 1.0, 2.0),
+                         ("gamma", 0.0, 0.5, 2.0), ("gamma", 0.0, 2.0, 2.0), ("gamma", inf, 1.0, 2.0),
+                         ("gamma", inf, 3.0, 2.0), ("invgamma", 0.0, 3.0, 2.0), ("invgamma", inf, 3.0, 2.0),
+                         ("exponential", 0.0, 2.0, None), ("exponential", inf, 2.0, None)):
+        assert e(F[fam], x, a, b, tr=True) == -inf, (fam, x, a, b)
+    # block log densities through the links (the wide-Slice model): invlogit(40) is exactly 1,
+    # invlogit(-800) and exp(-800) exactly 0, exp(800) is Inf
+    m, V = wide_slice(mamba, 2)
+    raw = wide_slice(mamba, 2, transform=False)[0]
+    for y in (40.0, -800.0):
+        assert oracle.block_logpdf(m, V[0], 0, [y, 0.0, 0.0, 0.0]) == -inf
+    for y in (-800.0, 800.0):
+        assert oracle.block_logpdf(m, V[0], 1, [y, 0.0, 0.0]) == -inf
+    # no transform: p = 0 with 3 successes of 10, p = 1 with 7 failures, lam = 0 with 4 events
+    # seen are impossible (-Inf, not NaN); p[3] = 1 with 7 of 7 and lam[1] = 0 with no event are not
+    assert oracle.block_logpdf(raw, V[0], 0, [0.0, 0.5, 0.5, 0.5]) == -inf
+    assert oracle.block_logpdf(raw, V[0], 0, [1.0, 0.5, 0.5, 0.5]) == -inf
+    assert oracle.block_logpdf(raw, V[0], 1, [1.0, 0.0, 1.0]) == -inf
+    assert math.isfinite(oracle.block_logpdf(raw, V[0], 0, [0.5, 0.0, 1.0, 0.5]))
+    assert math.isfinite(oracle.block_logpdf(raw, V[0], 1, [0.0, 1.0, 1.0]))
+
+
+WIDE_DATA = {"nn": [10.0, 12, 7, 20], "t": [1.0, 2.5, 0.5]}
+WIDE_FIXED = {"obs_bin": [3.0, 0, 7, 11], "obs_poi": [0.0, 4, 1]}
+# Window widths of the two Univariate Slice blocks on the link scale.  100 on logit(p) puts most
+# first candidates beyond |y| = 37, where invlogit is exactly 0 or 1; 3000 on log(lam) beyond
+# |y| = 746, where exp is exactly 0 or Inf.  Both are the widths the defect was found with: the
+# fixed code needs ~10 shrinks per coordinate there, nowhere near MMB_SLICE_MAX_SHRINK, so
+# neither was narrowed.
+WIDE_W_P, WIDE_W_LAM = 100.0, 3000.0
+
+
+def wide_slice(mamba, K, transform=True, seed=3):
+    """p[1..4] ~ Beta(1, 1) with Binomial observations, lam[1..3] ~ Gamma(1, 2) with Poisson
+    observations; two Univariate Slice blocks with windows far wider than the posterior."""
+    ir = mamba.ir
+    m = ir.Model(
+        obs_bin=ir.Stochastic(1, lambda nn, p: ir.Binomial(nn, p), False),
+        obs_poi=ir.Stochastic(1, lambda lam, t: ir.Poisson(lam * t), False),
+        p=ir.Stochastic(1, lambda: ir.Beta(1.0, 1.0)),
+        lam=ir.Stochastic(1, lambda: ir.Gamma(1.0, 2.0)))
+    m.setinputs(WIDE_DATA)
+    m.setsamplers([mamba.Slice("p", WIDE_W_P, mamba.Univariate, transform=transform),
+                   mamba.Slice("lam", WIDE_W_LAM, mamba.Univariate, transform=transform)])
+    rng = np.random.default_rng(seed)
+    inits = [{**WIDE_FIXED, "p": rng.uniform(0.05, 0.95, 4), "lam": rng.gamma(2.0, 1.0, 3)} for _ in range(K)]
+    return m, m.init_matrix(inits, K)
+
+
+def test_ir_wide_slice_stays_inside(mamba, oracle):
+    """Slice windows of width 100 (logit p) and 3000 (log lam) on Beta(1, 1) and Gamma(1, 2) priors:
+    candidates land where the link saturates (p exactly 0 or 1, lam exactly 0 or Inf).  Their log
+    density is -Inf, so they are shrunk away; when it was NaN (0 * -Inf) the shrink test
+    !(lp < p0) accepted them and most of the run was NaN (this very run: 14 747 of the 17 920 kept
+    values, after draws of p == 1 and lam == 0).  64 chains, 40 iterations, every iteration kept.
+    Also caught here: a Poisson rate lam * t that overflows to Inf (k log Inf - Inf = NaN)."""
+    m, V = wide_slice(mamba, 64)
+    st = oracle.new_state(m, V)
+    d = oracle.run(m, st, 40, burnin=0, thin=1, seed=17, nthreads=8)
+    assert d.shape == (40, 7, 64)
+    assert not np.isnan(d).any(), int(np.isnan(d).sum())
+    assert np.isfinite(d).all()
+    assert (d[:, :4, :] > 0).all() and (d[:, :4, :] < 1).all() and (d[:, 4:, :] > 0).all()
+    # and the chains move: no coordinate of any chain sits still over the run
+    assert (np.ptp(d, axis=0) > 0).all()
+
+
+def test_oracle_refuses_samplers_it_does_not_restate(mamba, oracle):
+    """oracle.c has no RWM update: run_chain would skip such a block, and a comparison against
+    it would be against chains that never moved.  The binding raises instead."""
+    m = mamba.ir.line_model().setinputs(mamba.model.LINE_DATA)
+    m.setsamplers([mamba.RWM("beta", 1.0), mamba.AMWG("s2", 1.0)])
+    v = mamba.model.line_init_matrix(2, seed=1)
+    V = m.init_matrix([{"y": [1.0, 3, 3, 3, 5], "beta": v[k, :2], "s2": v[k, 2]} for k in range(2)], 2)
+    with pytest.raises(NotImplementedError, match="does not restate"):
+        oracle.new_state(m, V)
+    tw = mamba.ir.line_model().setinputs(mamba.model.LINE_DATA).setsamplers([mamba.AMWG("beta", 1.0),
+                                                                            mamba.AMWG("s2", 1.0)])
+    tw.init_matrix([{"y": [1.0, 3, 3, 3, 5], "beta": v[k, :2], "s2": v[k, 2]} for k in range(2)], 2)
+    st = oracle.new_state(tw, V)
+    with pytest.raises(NotImplementedError, match="does not restate"):
+        oracle.run(m, st, 1)

@@ -44,6 +44,8 @@ def models():
     out.append(("seeds_ir_bench", m))
     import test_gpu_rwm as R
     out += R.ir_models()
+    import test_gpu_ir_families as F
+    out += F.ir_models()
     return out
 
 
