@@ -302,7 +302,9 @@ int mmb_reserve_draws(mmb_engine* e, int64_t nkept);
  * mmb_gr_range: per monitored param [min, max] over local chains/draws (for link()).
  * mmb_gr_partials: per-chain mean/covariance reduced over local chains, after optional
  * log/logit link (link_kind per param: 0 none, 1 log, 2 logit) and shift `shift[p]`;
- * out has mmb_gr_len() doubles: these are summed across GPUs (RCCL all-reduce). */
+ * out has mmb_gr_len() doubles: these are summed across GPUs (RCCL all-reduce).
+ * mmb_gr_partials and mmb_gr_allreduce serve at most 64 monitored values; a model that
+ * monitors more gets MMB_E_UNSUPPORTED (mmb_gr_range has no such limit). */
 int mmb_gr_range(mmb_engine* e, double* minmax /* 2*p */);
 int64_t mmb_gr_len(const mmb_engine* e);
 int mmb_gr_partials(mmb_engine* e, const int32_t* link_kind, const double* shift, double* out);

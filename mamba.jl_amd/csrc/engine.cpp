@@ -40,6 +40,7 @@ hipError_t mmb_launch_order_hist(int P, int j, int64_t n, int K, const double* d
                                  const uint64_t* prefix, int pass, unsigned long long* counts, hipStream_t st);
 hipError_t mmb_launch_gr_stats(int pmon, int64_t n, int K, const double* draws, const int32_t* link,
                                const double* shift, double* stats, hipStream_t st);
+int mmb_gr_pmax();
 hipError_t mmb_launch_chain_autocov(int P, int K, int64_t i0, int64_t i1, int nlags, const int64_t* lags,
                                     const double* draws, double* out, hipStream_t st);
 hipError_t mmb_launch_chain_mcse(int P, int K, int64_t i0, int64_t i1, int etype, int64_t bs, const double* draws,
@@ -2153,8 +2154,17 @@ int mmb_gr_range(mmb_engine* e, double* minmax) {
   return 0;
 }
 
+// gr.hip holds a chain's p x p covariance in thread-owned pairs: p <= mmb_gr_pmax()
+static int gr_width_check(mmb_engine* e) {
+  if (e->pmon > mmb_gr_pmax())
+    return fail(e, MMB_E_UNSUPPORTED, "Gelman-Rubin sums (gelmandiag, cor) serve at most %d monitored values; "
+                "this model monitors %d", mmb_gr_pmax(), e->pmon);
+  return 0;
+}
+
 int mmb_gr_partials(mmb_engine* e, const int32_t* link, const double* shift, double* out) {
   if (!e || !link || !shift || !out) return fail(e, MMB_E_ARG, "null argument");
+  if (int rc = gr_width_check(e)) return rc;
   if (e->n_kept < 2) return fail(e, MMB_E_STATE, "need >= 2 device-kept draws per chain");
   HIPCHK(e, hipSetDevice(e->device));
   const int p = e->pmon;
@@ -3177,6 +3187,8 @@ int mmb_gr_allreduce(mmb_comm* c, const int32_t* link, const double* shift, doub
   if (!c || !link || !shift || !out) return fail(nullptr, MMB_E_ARG, "null argument");
   mmb_engine* e0 = c->eng[0];
   const int p = c->p;
+  // every rank holds the same model, so all refuse alike before any collective
+  if (int wrc = gr_width_check(e0)) return wrc;
   int64_t nk = 0;
   int rc = comm_agree(c, 2, &nk);
   if (rc) return rc;

@@ -236,7 +236,7 @@ hipError_t mmb_launch_gr_range(int pmon, int64_t n, int K, const double* draws, 
   e = hipMemcpyAsync(h, part, (size_t)GR_RANGE_BLOCKS * pmon * 2 * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) {
-    double res[2 * GR_BIG_PMAX];
+    double* res = new double[(size_t)2 * pmon];  // pmon is unbounded here (node-IR models)
     for (int j = 0; j < pmon; ++j) {
       double lo = __builtin_inf(), hi = -__builtin_inf();
       for (int b = 0; b < GR_RANGE_BLOCKS; ++b) {
@@ -248,11 +248,15 @@ hipError_t mmb_launch_gr_range(int pmon, int64_t n, int K, const double* draws, 
     }
     e = hipMemcpyAsync(out, res, 2 * pmon * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
+    delete[] res;
   }
   delete[] h;
   (void)hipFreeAsync(part, st);
   return e;
 }
+
+// the widest model the Gelman-Rubin sums serve (engine.cpp refuses wider ones by name)
+int mmb_gr_pmax() { return GR_BIG_PMAX; }
 
 hipError_t mmb_launch_gr_stats(int pmon, int64_t n, int K, const double* draws, const int32_t* link,
                                const double* shift, double* stats, hipStream_t st) {

@@ -93,7 +93,8 @@ def pool_summary(parts, kg, n, bs, shift, allreduce_sum=None, allgather=None):
     sd = np.sqrt((Q - S1 * S1 / N) / (N - 1))
     sem = sd / np.sqrt(N)
     mcse = np.sqrt((D2 - D1 * D1 / m) / (m - 1) / m)
-    ess = np.minimum((sd / mcse) ** 2, n)                  # stats.jl:92 (n = iterations)
+    with np.errstate(invalid="ignore", divide="ignore"):   # a constant column: 0 / 0 -> NaN, as stats.jl
+        ess = np.minimum((sd / mcse) ** 2, n)              # stats.jl:92 (n = iterations)
     return np.stack([mean, sd, sem, mcse, ess], axis=1)
 
 

@@ -5,7 +5,8 @@ cases; the host pooling of the device partials (mamba.jl_amd/summary.py) against
 fed by an engine-shaped host shard whose partials/histograms restate the kernels'
 contracts (include/mamba_hip.h mmb_chain_summary / mmb_order_hist); and the sharded
 path at world size 2 over gloo, with the rank boundary inside a batch.  The device
-kernels themselves are checked in tests/test_gpu_parity.py.
+kernels themselves are checked in tests/test_gpu_parity.py (on sampler output) and in
+tests/test_gpu_pooled.py (on crafted draws, against tests/pooled_ref.py).
 """
 import math
 import os
