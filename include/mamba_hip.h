@@ -86,7 +86,9 @@ typedef enum {
                             e.g. doc/tutorial/line.jl:27-45 */
   MMB_SAMPLER_HMC = 6,   /* src/samplers/hmc.jl:47-65 */
   MMB_SAMPLER_MALA = 7,  /* src/samplers/mala.jl:43-58 */
-  MMB_SAMPLER_RWM = 8    /* src/samplers/rwm.jl:49-71 (additive: the ABI version is unchanged) */
+  MMB_SAMPLER_RWM = 8,   /* src/samplers/rwm.jl:49-71 (additive: the ABI version is unchanged) */
+  MMB_SAMPLER_DGS = 9    /* src/samplers/dgs.jl:56-126: discrete Gibbs sampling of one discrete node-IR node
+                            (additive: the ABI version is unchanged) */
 } mmb_sampler_kind;
 
 typedef enum { MMB_ADAPT_ALL = 0, MMB_ADAPT_BURNIN = 1, MMB_ADAPT_NONE = 2 } mmb_adapt;
@@ -158,11 +160,19 @@ typedef enum {
   MMB_IR_EXPONENTIAL = 5, /* Exponential(scale)                         PositiveDistribution  */
   MMB_IR_UNIFORM = 6,     /* Uniform(a, b), constant bounds lo/hi       bounded (affine logit) */
   MMB_IR_BETA = 7,        /* Beta(a, b)                                 UnitDistribution      */
-  MMB_IR_BINOMIAL = 8,    /* Binomial(n, p)     fixed (observed) nodes only */
-  MMB_IR_POISSON = 9,     /* Poisson(lambda)    fixed (observed) nodes only */
-  MMB_IR_BERNOULLI = 10,  /* Bernoulli(p)       fixed (observed) nodes only */
-  MMB_IR_LOGICAL = 11     /* Logical: expr[0] is the value (monitored logicals) */
+  MMB_IR_BINOMIAL = 8,    /* Binomial(n, p)     observed, or sampled by a DGS block (n data, max n <= 31:
+                             lo = 0, hi = max n, cterm = the lchoose table below) */
+  MMB_IR_POISSON = 9,     /* Poisson(lambda)    fixed (observed) nodes only (infinite support) */
+  MMB_IR_BERNOULLI = 10,  /* Bernoulli(p)       observed, or sampled by a DGS block (lo = 0, hi = 1) */
+  MMB_IR_LOGICAL = 11,    /* Logical: expr[0] is the value (monitored logicals) */
+  MMB_IR_CATEGORICAL = 12,     /* Categorical(p), support 1..K: no parameter expression; cterm = pool offset of
+                                  the K probabilities (shared by every element), lo = 1, hi = K */
+  MMB_IR_DISCRETEUNIFORM = 13  /* DiscreteUniform(a, b), constant integer bounds lo / hi */
 } mmb_ir_family;
+/* A sampled discrete node (Bernoulli, Binomial, Categorical, DiscreteUniform) is updated by a DGS block only,
+ * and a DGS block holds exactly one such node; its support is the integers lo..hi (Binomial: 0..n_i of
+ * element i), at most MMB_DGS_MAX_SUPPORT values.  Off the support its log density is -Inf. */
+#define MMB_DGS_MAX_SUPPORT 32
 
 /* expression code: one int32 word per op, op << 24 | arg; a push spills the previous top */
 enum {
@@ -173,6 +183,9 @@ enum {
   MMB_IR_OP_VALG = 4,   /* push state[arg + (int)pool[w + i]], w = the next code word */
   MMB_IR_OP_DATA = 5,   /* push pool[arg + i] */
   MMB_IR_OP_DATAS = 6,  /* push pool[arg] */
+  MMB_IR_OP_VALV = 7,   /* push state[arg + (int)state[w + i] - 1], w = the next code word: x[T] with T a
+                           sampled discrete node (state slots w .. w + len - 1) whose support lies in 1..len(x) */
+  MMB_IR_OP_DATAV = 8,  /* push pool[arg + (int)state[w + i] - 1], w = the next code word */
   MMB_IR_OP_ADD = 16, MMB_IR_OP_SUB = 17, MMB_IR_OP_MUL = 18, MMB_IR_OP_DIV = 19,
   MMB_IR_OP_NEG = 32, MMB_IR_OP_EXP = 33, MMB_IR_OP_LOG = 34, MMB_IR_OP_SQRT = 35,
   MMB_IR_OP_INVLOGIT = 36, MMB_IR_OP_LOGIT = 37, MMB_IR_OP_ABS = 38
@@ -188,8 +201,9 @@ typedef struct {
   int32_t off, len;  /* state slots (or pool offset) */
   int32_t expr[3];   /* code offsets of the distribution parameters (Distributions order), -1 none */
   int32_t cterm;     /* pool offset of a per-element constant (log binomial coefficient,
-                        -lgamma(k+1)) or -1 */
-  double lo, hi;     /* Uniform bounds */
+                        -lgamma(k+1)) or -1.  Sampled Binomial: a table of lchoose(n_i, k), k = 0..hi, per
+                        element i, at cterm + i (hi + 1) + k (0 where k > n_i).  Categorical: the K probabilities */
+  double lo, hi;     /* Uniform bounds; sampled discrete nodes and Categorical / DiscreteUniform: the support */
 } mmb_ir_node;
 
 /* logpdf!(m, x, block, transform) terms (simulation.jl:77-90): params \ targets in block

@@ -162,6 +162,7 @@ struct SweepArgs {
                          // slice_multi) instead of four per round
   int32_t amwg_probe;    // MMB_AMWG_PROBE=1 (tests only): near-threshold AMWG accept uniforms
                          // (mmb_math.h mmb_amwg_probe_factor)
+  int32_t ir_npool;      // node IR: entries of ir_pool (ir.h ev clamps a state-valued pool index to it)
 };
 
 // Wavefront pairing (sweep.hip order_chains_kernel): classes from the first MMB_ORDER_BLOCKS AMM

@@ -212,14 +212,21 @@ static int fail(mmb_engine* e, int code, const char* fmt, ...) {
       return fail((e), MMB_E_HIP, "%s failed: %s", #call, hipGetErrorString(_st));       \
   } while (0)
 
+// families a DGS block may sample (dgs.jl:6-8 DGSUnivariateDistribution, without the hypergeometrics)
+static bool ir_dgs_family(int fam) {
+  return fam == MMB_IR_BINOMIAL || fam == MMB_IR_BERNOULLI || fam == MMB_IR_CATEGORICAL ||
+         fam == MMB_IR_DISCRETEUNIFORM;
+}
+
 static int node_dim(const mmb_model_spec& s, const mmb_ir_model* ir, int node, bool* positive) {
   bool pos = false;
   int d = -1;
   if (s.model == MMB_MODEL_IR) {
-    // sampled nodes only: not fixed, not Logical, not a discrete family
+    // sampled nodes only: not fixed, not Logical; a discrete family only where a DGS block samples it
+    // (ir_validate checks that it is one)
     if (ir && node >= 0 && node < ir->nnodes) {
       const mmb_ir_node& n = ir->nodes[node];
-      const bool ok = !n.fixed && n.family >= MMB_IR_NORMAL && n.family <= MMB_IR_BETA;
+      const bool ok = !n.fixed && ((n.family >= MMB_IR_NORMAL && n.family <= MMB_IR_BETA) || ir_dgs_family(n.family));
       d = ok ? n.len : -1;
     }
   } else if (s.model == MMB_MODEL_LINE) {
@@ -248,8 +255,10 @@ static int tri(int i) { return i * (i + 1) / 2; }
 // amwg_dm, samplers.h amwg_lanes).  The table lists, per coordinate, the (term, element) pairs
 // that read it, then the pairs that read none; an MvNormal term's sigma must read none.  The
 // gather indices are data, so this is built per engine at upload, not in the JIT source.
+// (VALV / DATAV index with a state value: the index node's slot, and for VALV the first slot of the
+// indexed node, which names its owner; *dyn tells a caller that needs the exact slots)
 static void ir_expr_slots(const std::vector<int32_t>& code, const std::vector<double>& pool, int pc, int i,
-                          std::vector<int>& slots) {
+                          std::vector<int>& slots, bool* dyn = nullptr) {
   for (;; ++pc) {
     const int w = code[pc];
     const int op = (int)((uint32_t)w >> 24), arg = w & 0xffffff;
@@ -257,6 +266,11 @@ static void ir_expr_slots(const std::vector<int32_t>& code, const std::vector<do
     if (op == MMB_IR_OP_VAL) slots.push_back(arg);
     else if (op == MMB_IR_OP_VALI) slots.push_back(arg + i);
     else if (op == MMB_IR_OP_VALG) slots.push_back(arg + (int)pool[code[++pc] + i]);
+    else if (op == MMB_IR_OP_VALV || op == MMB_IR_OP_DATAV) {
+      if (op == MMB_IR_OP_VALV) slots.push_back(arg);
+      slots.push_back(code[++pc] + i);
+      if (dyn) *dyn = true;
+    }
   }
 }
 static bool ir_sep_table(const std::vector<mmb_ir_node>& nodes, const std::vector<int32_t>& code,
@@ -279,7 +293,9 @@ static bool ir_sep_table(const std::vector<mmb_ir_node>& nodes, const std::vecto
     const bool iso = N.family == MMB_IR_ISONORMAL;
     if (iso) {  // sigma (at element 0) must not read the block
       sl.clear();
-      ir_expr_slots(code, pool, N.expr[1], 0, sl);
+      bool dyn = false;
+      ir_expr_slots(code, pool, N.expr[1], 0, sl, &dyn);
+      if (dyn) return false;
       for (int q : sl)
         if (coord[q] >= 0) return false;
     }
@@ -287,8 +303,10 @@ static bool ir_sep_table(const std::vector<mmb_ir_node>& nodes, const std::vecto
     for (int i = 0; i < N.len; ++i) {
       sl.clear();
       if (!N.fixed) sl.push_back(N.off + i);
+      bool dyn = false;
       for (int k = 0; k < (iso ? 1 : 2); ++k)
-        if (N.expr[k] >= 0) ir_expr_slots(code, pool, N.expr[k], i, sl);
+        if (N.expr[k] >= 0) ir_expr_slots(code, pool, N.expr[k], i, sl, &dyn);
+      if (dyn) return false;  // a state-valued index: which coordinate the element reads is not fixed
       int c = -1;
       for (int q : sl) {
         const int cq = coord[q];
@@ -323,6 +341,7 @@ static int tune_len_of(int kind, int d) {
     case MMB_SAMPLER_HMC: return 2;   // [epsilon, L]     (HMCTune, hmc.jl:5-10)
     case MMB_SAMPLER_MALA: return 1;  // [epsilon]        (MALATune, mala.jl:5-9)
     case MMB_SAMPLER_RWM: return d;   // scale[d]         (RWMTune, rwm.jl:5-9)
+    case MMB_SAMPLER_DGS: return 0;   // no tuning state  (DGSTune holds only the mass function, dgs.jl:12-26)
     default: return 0;
   }
 }
@@ -355,7 +374,8 @@ const char* mmb_last_error(const mmb_engine* e) {
 
 // Device form of the node IR's expressions: a leaf immediately followed by a binary op
 // (postfix "... x leaf op") becomes one fused word MMB_IR_FUSED + 4 (leaf - 1) + (op - ADD)
-// with the leaf's argument (VALG keeps its second word): acc = acc op leaf instead of
+// with the leaf's argument (VALG, VALV and DATAV keep their second word; the leaves end at 8, so
+// the fused opcodes end at 64 + 4 * 7 + 3 = 95, within the opcode byte): acc = acc op leaf instead of
 // spill, load, reload -- the same operands in the same order, so results are bit-identical
 // to the oracle, which interprets the unfused code.  Each distinct expression start is
 // rewritten once (validated code: every expression ends in END); node offsets are remapped.
@@ -385,16 +405,17 @@ static void ir_fuse(const std::vector<int32_t>& code, std::vector<mmb_ir_node>& 
           out.push_back(code[pc]);
           if (op == MMB_IR_OP_END) break;
           if (op >= 1 && op < 16) {
-            const size_t nx = pc + (op == MMB_IR_OP_VALG ? 2 : 1);
+            const bool two = op == MMB_IR_OP_VALG || op == MMB_IR_OP_VALV || op == MMB_IR_OP_DATAV;
+            const size_t nx = pc + (two ? 2 : 1);
             const int bo = op_of(nx);
             if (bo >= MMB_IR_OP_ADD && bo <= MMB_IR_OP_DIV) {
               out.back() = (int32_t)(((uint32_t)(MMB_IR_FUSED + 4 * (op - 1) + (bo - MMB_IR_OP_ADD)) << 24) |
                                      ((uint32_t)code[pc] & 0xffffffu));
-              if (op == MMB_IR_OP_VALG) out.push_back(code[pc + 1]);
+              if (two) out.push_back(code[pc + 1]);
               pc = nx;  // the binary op is folded in
               continue;
             }
-            if (op == MMB_IR_OP_VALG) out.push_back(code[++pc]);
+            if (two) out.push_back(code[++pc]);
           }
         }
         it = start.find(s0);
@@ -484,7 +505,8 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
     }
     h.d = d;
     h.T = tri(d);
-    if (e->model == MMB_MODEL_IR && d > Mdl<MMB_MODEL_IR>::DMAX) {
+    // (a DGS block never unlists its node into lanes: it visits the elements one by one)
+    if (e->model == MMB_MODEL_IR && d > Mdl<MMB_MODEL_IR>::DMAX && s.sampler != MMB_SAMPLER_DGS) {
       delete e;
       return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: block %d has %d elements (max %d)", b, d,
                   Mdl<MMB_MODEL_IR>::DMAX);
@@ -589,10 +611,27 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
           return fail(nullptr, MMB_E_ARG, "block %d: unknown RWM proposal %d", b, s.form);
         }
         break;
+      case MMB_SAMPLER_DGS:  // dgs.jl:56-80: one discrete node per block (the host splits DGS([a, b]))
+        if (e->model != MMB_MODEL_IR) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: DGS samples discrete nodes of node-IR models only", b);
+        }
+        if (s.nnodes != 1 || !ir_dgs_family(ir->nodes[s.nodes[0]].family)) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: a DGS block holds one Bernoulli, Binomial, Categorical or "
+                      "DiscreteUniform node", b);
+        }
+        break;
       default:
         delete e;
         return fail(nullptr, MMB_E_ARG, "unknown sampler kind %d", s.sampler);
     }
+    if (e->model == MMB_MODEL_IR && s.sampler != MMB_SAMPLER_DGS)
+      for (int a = 0; a < s.nnodes; ++a)
+        if (ir_dgs_family(ir->nodes[s.nodes[a]].family)) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: discrete node %d can be sampled by a DGS block only", b, s.nodes[a]);
+        }
     h.tune_len = tune_len_of(s.sampler, d);
     e->kinds |= 1u << s.sampler;
     e->blocks.push_back(h);
@@ -689,6 +728,22 @@ static int ir_check_expr(const mmb_ir_model* ir, int pc, int len, int* depth, in
         }
         case MMB_IR_OP_DATA: if ((int64_t)arg + len > ir->npool) return -1; break;
         case MMB_IR_OP_DATAS: if ((int64_t)arg >= ir->npool) return -1; break;
+        case MMB_IR_OP_VALV:
+        case MMB_IR_OP_DATAV: {
+          // x[T]: the second word is the first state slot of a sampled discrete node T of exactly
+          // `len` elements, whose support lo..hi (integers, >= 1) stays inside the indexed table
+          if (++pc >= ir->ncode) return -1;
+          const int64_t w2 = ir->code[pc];
+          const mmb_ir_node* T = nullptr;
+          for (int q = 0; q < ir->nnodes; ++q) {
+            const mmb_ir_node& Q = ir->nodes[q];
+            if (!Q.fixed && ir_dgs_family(Q.family) && Q.off == w2 && Q.len == len) T = &Q;
+          }
+          if (!T || !(T->lo >= 1.0) || !(T->hi >= T->lo) || !(T->hi < 16777216.0)) return -1;
+          const int64_t top = (int64_t)arg + (int64_t)T->hi - 1;
+          if (top >= (op == MMB_IR_OP_VALV ? (int64_t)ir->nvalues : ir->npool)) return -1;
+          break;
+        }
         default: return -1;
       }
       ++sp;
@@ -717,18 +772,68 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
   int depth = 0;
   for (int n = 0; n < ir->nnodes; ++n) {
     const mmb_ir_node& N = ir->nodes[n];
-    if (N.family < MMB_IR_NORMAL || N.family > MMB_IR_LOGICAL || N.len < 1)
+    if (N.family < MMB_IR_NORMAL || N.family > MMB_IR_DISCRETEUNIFORM || N.len < 1)
       return fail(nullptr, MMB_E_ARG, "node IR: node %d has a bad family or length", n);
     if (N.family != MMB_IR_LOGICAL) {
       const int64_t end = (int64_t)N.off + N.len;
       if (N.off < 0 || end > (N.fixed ? ir->npool : (int64_t)ir->nvalues))
         return fail(nullptr, MMB_E_ARG, "node IR: node %d values out of range", n);
     }
-    if (N.family >= MMB_IR_BINOMIAL && N.family <= MMB_IR_BERNOULLI && !N.fixed)
-      return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: discrete node %d must be fixed (observed)", n);
-    if (N.cterm >= 0 && (int64_t)N.cterm + N.len > ir->npool)
-      return fail(nullptr, MMB_E_ARG, "node IR: node %d constant term out of range", n);
-    const int nexpr = N.family == MMB_IR_LOGICAL || N.family == MMB_IR_EXPONENTIAL || N.family == MMB_IR_POISSON ||
+    if (N.family == MMB_IR_POISSON && !N.fixed)  // (infinite support: no DGS)
+      return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: Poisson node %d must be fixed (observed)", n);
+    const bool dgs = !N.fixed && ir_dgs_family(N.family);
+    if (dgs) {  // a sampled discrete node: in exactly the DGS blocks, one node each (create_impl), never another kind
+      bool in_dgs = false;
+      for (int b = 0; b < spec->nblocks; ++b)
+        for (int a = 0; a < spec->blocks[b].nnodes && a < MMB_MAX_NODES_PER_BLOCK; ++a)
+          if (spec->blocks[b].nodes[a] == n) {
+            if (spec->blocks[b].sampler != MMB_SAMPLER_DGS)
+              return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d can be sampled by a DGS block only", n);
+            in_dgs = true;
+          }
+      if (!in_dgs) return fail(nullptr, MMB_E_ARG, "node IR: sampled discrete node %d is in no DGS block", n);
+    }
+    // integer support lo..hi of at most MMB_DGS_MAX_SUPPORT values: Categorical and DiscreteUniform
+    // always (their density reads it), Bernoulli and Binomial when sampled
+    if (dgs || N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM) {
+      const bool ints = N.lo == std::floor(N.lo) && N.hi == std::floor(N.hi) && std::fabs(N.lo) < 16777216.0;
+      if (!ints || !(N.hi >= N.lo) || (dgs && N.hi - N.lo + 1.0 > (double)MMB_DGS_MAX_SUPPORT))
+        return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d needs an integer support of at most %d values", n,
+                    MMB_DGS_MAX_SUPPORT);
+      if (N.family == MMB_IR_CATEGORICAL && N.lo != 1.0)
+        return fail(nullptr, MMB_E_ARG, "node IR: Categorical node %d has support 1..K", n);
+      if ((N.family == MMB_IR_BINOMIAL || N.family == MMB_IR_BERNOULLI) &&
+          (N.lo != 0.0 || (N.family == MMB_IR_BERNOULLI && N.hi != 1.0)))
+        return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d has a bad support", n);
+    }
+    {  // constant table: per element; sampled Binomial (element, value); Categorical K probabilities
+      int64_t nct = N.len;
+      if (N.family == MMB_IR_CATEGORICAL) nct = (int64_t)N.hi;
+      else if (N.family == MMB_IR_BINOMIAL && dgs) nct = (int64_t)N.len * ((int64_t)N.hi + 1);
+      if ((N.family == MMB_IR_CATEGORICAL || (N.family == MMB_IR_BINOMIAL && dgs)) && N.cterm < 0)
+        return fail(nullptr, MMB_E_ARG, "node IR: node %d needs its constant table", n);
+      if (N.cterm >= 0 && (int64_t)N.cterm + nct > ir->npool)
+        return fail(nullptr, MMB_E_ARG, "node IR: node %d constant term out of range", n);
+    }
+    if (N.family == MMB_IR_BINOMIAL && dgs) {
+      // n is data, one DATA / DATAS word, so that the support 0..n_i of every element is known here
+      const int pc = N.expr[0];
+      if (pc < 0 || pc + 1 >= ir->ncode || ir->code[pc + 1] != 0)
+        return fail(nullptr, MMB_E_ARG, "node IR: sampled Binomial node %d: n must be one data word", n);
+      const int op = (int)((uint32_t)ir->code[pc] >> 24), arg = ir->code[pc] & 0xffffff;
+      if (op != MMB_IR_OP_DATA && op != MMB_IR_OP_DATAS)
+        return fail(nullptr, MMB_E_ARG, "node IR: sampled Binomial node %d: n must be one data word", n);
+      for (int i = 0; i < N.len; ++i) {
+        const int64_t at = (int64_t)arg + (op == MMB_IR_OP_DATA ? i : 0);
+        if (at >= ir->npool) return fail(nullptr, MMB_E_ARG, "node IR: node %d parameter 0 has invalid code", n);
+        const double nn = ir->pool[at];
+        if (!(nn >= 0.0 && nn <= N.hi && nn == std::floor(nn)))
+          return fail(nullptr, MMB_E_ARG, "node IR: sampled Binomial node %d: n[%d] must be an integer in 0..%d", n, i,
+                      (int)N.hi);
+      }
+    }
+    const int nexpr = N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM ? 0
+                      : N.family == MMB_IR_LOGICAL || N.family == MMB_IR_EXPONENTIAL || N.family == MMB_IR_POISSON ||
                               N.family == MMB_IR_BERNOULLI ? 1 : 2;
     for (int k = 0; k < 3; ++k) {
       if (k >= nexpr) {
@@ -752,6 +857,8 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
     for (int t = 0; t < B.nterms; ++t)
       if (B.term[t] < 0 || B.term[t] >= ir->nnodes || ir->nodes[B.term[t]].family == MMB_IR_LOGICAL)
         return fail(nullptr, MMB_E_ARG, "node IR: block %d term %d invalid", b, t);
+    if (spec->blocks[b].sampler == MMB_SAMPLER_DGS && B.term[0] != spec->blocks[b].nodes[0])
+      return fail(nullptr, MMB_E_ARG, "node IR: DGS block %d: its terms are its node, then the node's targets", b);
     if (!gibbs) {
       if (B.gibbs_family != 0) return fail(nullptr, MMB_E_ARG, "node IR: block %d is not a Gibbs block", b);
       continue;
@@ -795,6 +902,11 @@ static void ir_jit_params(const mmb_model_spec* spec, const mmb_ir_model* ir, un
   if (*dmax == 0) *dmax = Mdl<MMB_MODEL_IR>::DMAX;  // no AMM block: the factorization is not compiled
 }
 
+// The generator (ir_jit.cpp) writes no code for DGS blocks, the discrete families they sample or the
+// state-indexed leaves VALV / DATAV, which only such schemes hold: it declines those schemes whole
+static const char* const kJitNoDgs = "the specialised kernel declines schemes with DGS blocks: sampled discrete "
+                                     "nodes and state-indexed gathers are not generated";
+
 // The specialised kernel of a node-IR engine (ir_jit.cpp); on any failure the interpreter
 // kernel runs (jit_info says why).  MMB_IR_JIT=0 selects the interpreter.
 static void ir_jit_setup(mmb_engine* e, const mmb_model_spec* spec, const mmb_ir_model* ir) {
@@ -806,6 +918,10 @@ static void ir_jit_setup(mmb_engine* e, const mmb_model_spec* spec, const mmb_ir
   unsigned kinds = 0;
   int dmax = 0;
   ir_jit_params(spec, ir, &kinds, &dmax);
+  if (kinds & (1u << MMB_SAMPLER_DGS)) {
+    e->jit_info = std::string("interpreter (") + kJitNoDgs + ")";
+    return;
+  }
   std::vector<char> code;
   std::string info;
   if (mmb_ir_jit_obtain(mmb_ir_jit_source(*spec, *ir, kinds, dmax), &code, &info)) {
@@ -857,6 +973,10 @@ int mmb_ir_jit_prebuild(const mmb_model_spec* spec, const mmb_ir_model* ir, char
   unsigned kinds = 0;
   int dmax = 0;
   ir_jit_params(spec, ir, &kinds, &dmax);
+  if (kinds & (1u << MMB_SAMPLER_DGS)) {
+    if (info && n > 0) snprintf(info, (size_t)n, "%s", kJitNoDgs);
+    return fail(nullptr, MMB_E_UNSUPPORTED, "%s", kJitNoDgs);
+  }
   std::vector<char> code;
   std::string msg;
   rc = mmb_ir_jit_obtain(mmb_ir_jit_source(*spec, *ir, kinds, dmax), &code, &msg);
@@ -871,6 +991,7 @@ int mmb_ir_jit_source_text(const mmb_model_spec* spec, const mmb_ir_model* ir, c
   unsigned kinds = 0;
   int dmax = 0;
   ir_jit_params(spec, ir, &kinds, &dmax);
+  if (kinds & (1u << MMB_SAMPLER_DGS)) return fail(nullptr, MMB_E_UNSUPPORTED, "%s", kJitNoDgs);
   const std::string src = mmb_ir_jit_source(*spec, *ir, kinds, dmax);
   if (buf && n > 0) snprintf(buf, (size_t)n, "%s", src.c_str());
   return (int)std::min<size_t>(src.size(), (size_t)INT32_MAX);
@@ -1101,6 +1222,25 @@ static void from_device_layout(const mmb_engine* e, const double* dv, double* v)
 int mmb_set_values(mmb_engine* e, const double* values) {
   if (!e || !values) return fail(e, MMB_E_ARG, "null argument");
   if (!e->d_vals) return fail(e, MMB_E_STATE, "mmb_init_chains not called");
+  if (e->model == MMB_MODEL_IR && (e->kinds & (1u << MMB_SAMPLER_DGS))) {
+    // sampled discrete nodes: every value inside its support, which is what bounds the state-indexed
+    // gathers x[T] (ir.h ev) and the constant-table lookups of the kernels
+    for (const mmb_ir_node& N : e->ir_nodes) {
+      if (N.fixed || !ir_dgs_family(N.family)) continue;
+      for (int64_t k = 0; k < e->K; ++k)
+        for (int i = 0; i < N.len; ++i) {
+          const double x = values[k * e->P + N.off + i];
+          double hi = N.hi;
+          if (N.family == MMB_IR_BINOMIAL) {  // (one DATA / DATAS word: ir_validate)
+            const int w = e->ir_code[N.expr[0]];
+            hi = e->ir_pool[(w & 0xffffff) + ((int)((uint32_t)w >> 24) == MMB_IR_OP_DATA ? i : 0)];
+          }
+          if (!(x >= N.lo && x <= hi && x == std::floor(x)))
+            return fail(e, MMB_E_ARG, "chain %lld: value %g of discrete node element %d is outside its support %g..%g",
+                        (long long)k, x, i, N.lo, hi);
+        }
+    }
+  }
   ++e->xepoch;
   std::vector<double> h((size_t)e->K * e->VS);
   for (int64_t k = 0; k < e->K; ++k) to_device_layout(e, values + k * e->P, h.data() + k * e->VS);
@@ -1338,6 +1478,7 @@ static void fill_args(const mmb_engine* e, SweepArgs& A) {
     A.ir_pmon = e->pmon;
     A.ir_vs = e->VS;
     A.ir_red0 = e->P;  // Gibbs reduction slots follow the values
+    A.ir_npool = (int32_t)e->ir_pool.size();
     // AMM scratch mat[TP] | z2 | vv | mv | ia (+ pchol32's reciprocal slot), the state (and its
     // candidate copy), the expression stack (ir.h Mdl::load; interpreter: Mdl<IR>::AMM_DBL, TP = 528)
     A.ir_amm = (e->kinds & (1u << MMB_SAMPLER_AMM)) ? (int32_t)(e->TP + 4 * Mdl<MMB_MODEL_IR>::DP + 2) : 0;
@@ -2575,6 +2716,9 @@ static int pr_plan(mmb_engine* e, int nnodes, const int32_t* nodes, PrPlan& pl) 
   for (int a = 0; a < nnodes; ++a) {
     const mmb_ir_node& N = e->ir_nodes[nodes[a]];
     if (!N.fixed) return fail(e, MMB_E_ARG, "node id %d is not an observed Stochastic node of the model", nodes[a]);
+    if (N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM)
+      return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d: Categorical and DiscreteUniform variates are not lowered",
+                  nodes[a]);
     const bool gam = N.family == MMB_IR_GAMMA || N.family == MMB_IR_INVGAMMA || N.family == MMB_IR_BETA;
     if (gam && !mmb_pr_gblock_ok(nodes[a], N.len))
       return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d (length %d) does not fit the element blocks of the "
@@ -2849,6 +2993,7 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
       case MMB_SAMPLER_HMC: s += 8.0 * 2; break;   // epsilon, L (read only)
       case MMB_SAMPLER_MALA: s += 8.0; break;
       case MMB_SAMPLER_RWM: s += 8.0 * h.d; break;  // scale (read only)
+      case MMB_SAMPLER_DGS: break;  // no tune state; the masses stay in registers (samplers.h dgs)
       default: break;
     }
   }

@@ -125,7 +125,17 @@ struct Mdl<MMB_MODEL_IR> {
           v = vals[arg + (int)A.ir_pool[wn + i]];
           wn = ir_const_ref(A.ir_code, pc + 1);
         } else if (lk == MMB_IR_OP_DATA) v = A.ir_pool[arg + i];
-        else v = A.ir_pool[arg];  // MMB_IR_OP_DATAS
+        else if (lk == MMB_IR_OP_VALV || lk == MMB_IR_OP_DATAV) {
+          // x[T], T a sampled discrete node at state slots wn ..: the host checked T's support against
+          // len(x) and the engine every value it uploads; the index is still clamped to the table
+          // (state row / pool), so no value -- a NaN in draws set by a caller, say -- reads outside it
+          ++pc;
+          const int lim = (lk == MMB_IR_OP_VALV ? A.ir_red0 : A.ir_npool) - 1 - arg;
+          int t = (int)vals[wn + i] - 1;
+          t = t < 0 ? 0 : (t > lim ? lim : t);
+          v = lk == MMB_IR_OP_VALV ? vals[arg + t] : A.ir_pool[arg + t];
+          wn = ir_const_ref(A.ir_code, pc + 1);
+        } else v = A.ir_pool[arg];  // MMB_IR_OP_DATAS
         if (op < 16) {
           // the bottom slot is never popped: no spill for an expression's first leaf
           if (sp > 0) stk[sp * G + lane] = acc;
@@ -153,6 +163,25 @@ struct Mdl<MMB_MODEL_IR> {
     }
   }
 
+  // logpdf_sub of element i of a node at value x (distributionstruct.jl:138-140).  The constant term is
+  // per element, except a sampled Binomial's (indexed by element and value) and Categorical's (its
+  // probability table, indexed by value); a sampled discrete node's value is state, so its support is
+  // tested here (an observed one's was checked by the host)
+  __device__ __forceinline__ static double elem_lp(const SweepArgs& A, const mmb_ir_node& N, int i, double x,
+                                                   const double* vals, double* stk, int lane, int tr) {
+    const double a = N.expr[0] >= 0 ? ev(A, N.expr[0], i, vals, stk, lane) : 0.0;
+    const double b = N.expr[1] >= 0 ? ev(A, N.expr[1], i, vals, stk, lane) : 0.0;
+    double ct = 0.0;
+    if (N.cterm >= 0) {
+      const int ci = mmb_ir_cterm_index(N.family, N.fixed, i, x, N.lo, N.hi);
+      ct = ci >= 0 ? A.ir_pool[N.cterm + ci] : 0.0;
+    }
+    if (!N.fixed && (N.family == MMB_IR_BINOMIAL || N.family == MMB_IR_BERNOULLI) &&
+        !mmb_ir_discrete_in(N.family, x, a, N.lo, N.hi))
+      return -__builtin_inf();
+    return mmb_ir_lp(N.family, x, a, b, ct, tr, N.lo, N.hi);
+  }
+
   // logpdf(node[, transform]) (dependent.jl:207-213 -> logpdf_sub), group-uniform result
   __device__ static double node_lp(const SweepArgs& A, int n, const double* vals, double* stk,
                                    const Grp<G>& g, int tr) {
@@ -172,12 +201,7 @@ struct Mdl<MMB_MODEL_IR> {
       return bad != 0.0 ? -__builtin_inf() : d_iso(N.len, sig, ss);
     }
     double acc = 0.0;
-    for (int i = lane; i < N.len; i += G) {
-      const double a = N.expr[0] >= 0 ? ev(A, N.expr[0], i, vals, stk, lane) : 0.0;
-      const double b = N.expr[1] >= 0 ? ev(A, N.expr[1], i, vals, stk, lane) : 0.0;
-      const double ct = N.cterm >= 0 ? A.ir_pool[N.cterm + i] : 0.0;
-      acc = acc + mmb_ir_lp(N.family, src[i], a, b, ct, tr, N.lo, N.hi);
-    }
+    for (int i = lane; i < N.len; i += G) acc = acc + elem_lp(A, N, i, src[i], vals, stk, lane, tr);
     return g.sum(acc);
   }
 
@@ -501,6 +525,49 @@ struct Mdl<MMB_MODEL_IR> {
       if (!NOPROP) s.prop[off] = v;
     }
     grp_sync();
+  }
+
+  // DGS blocks (samplers.h dgs; dgs.jl:56-126): one sampled discrete node per block.  dgs_elems: its
+  // length.  dgs_support: element e's support, the n integers from *lo up (Binomial: 0..n_e, n_e data;
+  // the others the node's lo..hi), n <= MMB_DGS_MAX_SUPPORT by the host's and the engine's checks and
+  // capped here.  dgs_set: the element's state slot (and its mirror in prop).  dgs_lp: logpdf(d, v) of
+  // element e alone plus logpdf(model, node.targets), targets in topological order with the early
+  // exit on a non-finite running sum (simulation.jl:84); the block's term list is the node, then
+  // its targets (ir.py).  All group-uniform.
+  __device__ __forceinline__ static int dgs_elems(const St& s, const DBlock& B) {
+    return ir_const_ref(s.nodes, B.nodes[0]).len;
+  }
+  __device__ __forceinline__ static int dgs_support(const SweepArgs& A, const DBlock& B, const St& s, int e, int lane,
+                                                    double* lo) {
+    const mmb_ir_node& N = ir_const_ref(s.nodes, B.nodes[0]);
+    double hi = N.hi;
+    *lo = N.lo;
+    if (N.family == MMB_IR_BINOMIAL) hi = ev(A, N.expr[0], e, s.cur, s.stk, lane);
+    const double n = hi - *lo + 1.0;
+    return n >= 1.0 ? (n < (double)MMB_DGS_MAX_SUPPORT ? (int)n : MMB_DGS_MAX_SUPPORT) : 1;
+  }
+  __device__ __forceinline__ static double dgs_get(const DBlock& B, const St& s, int e) {
+    return s.cur[ir_const_ref(s.nodes, B.nodes[0]).off + e];
+  }
+  __device__ __forceinline__ static void dgs_set(const DBlock& B, St& s, int e, double v, int lane) {
+    const int slot = ir_const_ref(s.nodes, B.nodes[0]).off + e;
+    grp_sync();
+    if (lane == 0) {
+      s.cur[slot] = v;
+      if (!NOPROP) s.prop[slot] = v;
+    }
+    grp_sync();
+  }
+  __device__ static double dgs_lp(const SweepArgs& A, const DBlock& B, const St& s, const Grp<G>& g, int e, double v) {
+    const mmb_ir_block& IB = ir_const_ref(A.ir_blocks, B.ir_blk);
+    const mmb_ir_node& N = ir_const_ref(s.nodes, B.nodes[0]);
+    const double own = elem_lp(A, N, e, v, s.cur, s.stk, g.lane, 0);
+    double lp = 0.0;
+    for (int t = 1; t < IB.nterms; ++t) {
+      lp += node_lp(A, IB.term[t], s.cur, s.stk, g, 0);
+      if (!isfinite(lp)) break;
+    }
+    return own + lp;
   }
 
   // sim[i, :, 1] = unlist(m, true) (mcmc.jl:76-77): monitored nodes in Chains order; logicals

@@ -97,6 +97,28 @@ MMB_HD double mmb_ir_normal_lb(double x, double a, double b, double lb) {
  * product, so interior values keep their bits. */
 MMB_HD double mmb_ir_xlogy(double c, double x, double lx) { return (c == 0.0 && x == 0.0) ? 0.0 : c * lx; }
 
+/* insupport of the discrete families: x an integer in [lo, hi] (NaN: false) */
+MMB_HD int mmb_ir_int_in(double x, double lo, double hi) { return lo <= x && x <= hi && x == floor(x); }
+
+/* A sampled discrete node (updated by a DGS block, samplers.h dgs): its value is state, not a
+ * host-checked observation, so insupport is tested here.  (lo, hi) = the node's support bounds;
+ * Binomial's upper bound is the element's own n.  Categorical and DiscreteUniform test theirs in
+ * mmb_ir_lp.  Observed nodes never come here: their densities keep their bits. */
+MMB_HD int mmb_ir_discrete_in(int fam, double x, double n, double lo, double hi) {
+  if (fam == MMB_IR_BINOMIAL) return mmb_ir_int_in(x, 0.0, n);
+  if (fam == MMB_IR_BERNOULLI) return x == 0.0 || x == 1.0;
+  return mmb_ir_int_in(x, lo, hi);
+}
+
+/* Offset into a node's constant table (mmb_ir_node.cterm) of element i with value x, -1 when x has no
+ * entry: per element for observed nodes; lchoose(n_i, k) at i (hi + 1) + k for a sampled Binomial
+ * node; p[x] at x - 1 for Categorical. */
+MMB_HD int mmb_ir_cterm_index(int fam, int fixed, int i, double x, double lo, double hi) {
+  if (fam == MMB_IR_CATEGORICAL) return mmb_ir_int_in(x, lo, hi) ? (int)x - 1 : -1;
+  if (fam == MMB_IR_BINOMIAL && !fixed) return mmb_ir_int_in(x, 0.0, hi) ? i * ((int)hi + 1) + (int)x : -1;
+  return i;
+}
+
 MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr, double lo, double hi) {
   const double NINF = -__builtin_inf(), INF = __builtin_inf();
   switch (fam) {
@@ -148,6 +170,12 @@ MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr
     }
     case MMB_IR_BERNOULLI: /* x ? log p : log(1 - p) */
       return x == 1.0 ? mmb_log(a) : mmb_log(1.0 - a);
+    case MMB_IR_CATEGORICAL: /* log p[x], x in 1..K = lo..hi; ct = p[x] (looked up by the caller) */
+      if (!mmb_ir_int_in(x, lo, hi)) return NINF;
+      return mmb_log(ct);
+    case MMB_IR_DISCRETEUNIFORM: /* -log(b - a + 1) on the integers a..b */
+      if (!mmb_ir_int_in(x, lo, hi)) return NINF;
+      return -mmb_log(hi - lo + 1.0);
     default:
       return 0.0; /* Logical nodes contribute 0 */
   }

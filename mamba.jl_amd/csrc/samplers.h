@@ -275,6 +275,56 @@ struct Smp {
     M::relist(B, s, g, v);
   }
 
+  // ---------------------------------------------------------------- DGS
+  // dgs.jl:56-126 (DGS(params), sample!, mass): the full conditional of each element of the block's
+  // one discrete node, by enumeration of the element's support (node-IR models; M::dgs_* in ir.h).
+  // Elements are updated in order and each sees the earlier ones' new values.  For element e, the
+  // k-th support value (ascending) is written into the state and mass_k = exp(logpdf(d_e, s_k) +
+  // logpdf(model, targets)) is evaluated by all 32 lanes (the targets' element terms lane-parallel,
+  // M::dgs_lp); lane k keeps mass_k in a register -- at most 32 masses, one per lane, nothing goes
+  // to memory.  Then, the same on every lane, psum = mass_0 + mass_1 + ... in k order,
+  // probs_k = psum > 0 ? mass_k / psum : 1 / n (dgs.jl:119-121), and the value is the smallest k
+  // whose running sum probs_0 + ... + probs_k exceeds u (the last value if none does), u = uniform #e
+  // of the block's MMB_SUB_UNIFORM stream: rand(Categorical(probs)) by inversion.  No tune state.
+  // A psum that is not finite (a mass overflowed to +Inf, or a NaN log density) has no probability
+  // vector: the reference throws inside Categorical(probs); here the element keeps the value it had
+  // before the update.  u is indexed by the element, so that draws nothing out of order.
+  __device__ __forceinline__ static void dgs(const SweepArgs& A, const DBlock& B, const mmb_rng& ru, St& s,
+                                             const Grp<G>& g) {
+    static_assert(G == 32, "DGS keeps one mass per lane of a 32-lane group");
+    const int len = M::dgs_elems(s, B);
+    for (int e = 0; e < len; ++e) {
+      double lo;
+      const int n = M::dgs_support(A, B, s, e, g.lane, &lo);
+      const double old = M::dgs_get(B, s, e);
+      double mass = 0.0;
+      for (int k = 0; k < n; ++k) {
+        M::dgs_set(B, s, e, lo + (double)k, g.lane);
+        const double m = mmb_exp(M::dgs_lp(A, B, s, g, e, lo + (double)k));
+        mass = g.lane == k ? m : mass;
+      }
+      double psum = 0.0;
+      for (int k = 0; k < n; ++k) psum = psum + lane_value(mass, k);
+      const double u = mmb_uniform(&ru, (uint32_t)e);
+      double v = old;
+      if (isfinite(psum)) {
+        const double unif = 1.0 / (double)n;
+        double cum = 0.0;
+        int pick = n - 1;
+        bool found = false;
+        for (int k = 0; k < n; ++k) {
+          cum = cum + (psum > 0.0 ? lane_value(mass, k) / psum : unif);
+          if (!found && cum > u) {
+            pick = k;
+            found = true;
+          }
+        }
+        v = lo + (double)pick;
+      }
+      M::dgs_set(B, s, e, v, g.lane);
+    }
+  }
+
   // ---------------------------------------------------------------- pivoted Cholesky
   // cholfact(Hermitian(S), Val{true}) restated in LAPACK dpstf2('U', tol = 0) op order
   // (oracle.c orc_pchol): pivot = first maximum of the remaining diagonal in position

@@ -152,6 +152,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
         case MMB_SAMPLER_RWM:
           if constexpr ((KINDS >> MMB_SAMPLER_RWM) & 1u) S::rwm(A, B, c, chain, it, b, rn, ru, s, l, g, pk);
           break;
+        case MMB_SAMPLER_DGS:
+          if constexpr ((KINDS >> MMB_SAMPLER_DGS) & 1u) S::dgs(A, B, ru, s, g);
+          break;
         case MMB_SAMPLER_GIBBS: if constexpr ((KINDS >> MMB_SAMPLER_GIBBS) & 1u) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
           const mmb_rng gu = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_U);
@@ -216,4 +219,7 @@ constexpr unsigned K_IR = (1u << MMB_SAMPLER_AMWG) | (1u << MMB_SAMPLER_AMM) | (
 // RWM is compiled only into kernels of their own, which schemes that hold an RWM block take
 // (sweep.hip): the instantiations above keep their masks, and so their code
 constexpr unsigned K_RWM = 1u << MMB_SAMPLER_RWM;
+// DGS likewise (node-IR models only): one more instantiation, which also holds RWM, so that a scheme
+// may mix DGS blocks with every other kind
+constexpr unsigned K_DGS = 1u << MMB_SAMPLER_DGS;
 

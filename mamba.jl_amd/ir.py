@@ -21,8 +21,18 @@ per-node stack code, the block term lists of logpdf! (simulation.jl:77-90: param
 in block order, then targets in topological order) and the monitored nodes.
 
 Supported: Normal, MvNormal(mu, sigma) (isotropic), InverseGamma, Gamma, Exponential,
-Uniform (constant bounds), Beta for sampled nodes; Binomial, Poisson, Bernoulli for fixed
-nodes; + - * / neg abs exp log sqrt invlogit logit, x**2; blocks of <= 32 elements.
+Uniform (constant bounds), Beta for sampled nodes; Binomial, Poisson, Bernoulli, Categorical,
+DiscreteUniform for fixed nodes; + - * / neg abs exp log sqrt invlogit logit, x**2; blocks of
+<= 32 elements.
+
+Discrete nodes (src/samplers/dgs.jl): a Bernoulli, Binomial (n data), Categorical(p) (p a constant
+list or a data vector shared by every element, support 1..K) or DiscreteUniform(a, b) (constant
+integer bounds) node may be sampled, by a `DGS` block only; Poisson stays observed (infinite
+support).  A sampled element's support holds at most 32 values (one mass per lane of the chain's
+32-lane group): Binomial n <= 31, K <= 32, b - a <= 31.  DGS(["a", "b"]) becomes one device block
+per node, in order (the reference loops over its keys, dgs.jl:61-80); a DGS node may be longer
+than 32 elements.  `x[T]` with T a sampled discrete node gathers by the state (x a sampled node or
+a data vector; T's support within 1..len(x), T as long as the expression).
 
 User Gibbs blocks (ABI 10): `Sampler(params, f)` (src/samplers/sampler.jl:20-24) whose closure
 returns `rand(Normal(mu, sigma))`, `rand(InverseGamma(shape, scale))` or `rand(Gamma(shape,
@@ -178,6 +188,31 @@ def Poisson(lam): return Dist(abi.MMB_IR_POISSON, lam)
 def Bernoulli(p): return Dist(abi.MMB_IR_BERNOULLI, p)
 
 
+def Categorical(p):
+    """Categorical(p): support 1..K; p a list of K constants or a data vector (an input), the same
+    for every element of the node."""
+    d = Dist(abi.MMB_IR_CATEGORICAL)
+    if isinstance(p, Ref):
+        d.p = p
+    elif isinstance(p, Expr):
+        raise ArgumentError("Categorical(p): p is a constant list or a data vector")
+    else:
+        d.p = np.atleast_1d(np.asarray(p, dtype=np.float64)).ravel()
+    return d
+
+
+def DiscreteUniform(a, b):
+    """DiscreteUniform(a, b): the integers a..b, constant bounds."""
+    for v in (a, b):
+        if isinstance(v, Expr) or isinstance(v, bool) or v != int(v):
+            raise ArgumentError("DiscreteUniform(a, b): constant integer bounds")
+    if int(b) < int(a):
+        raise ArgumentError("DiscreteUniform(a, b): a <= b")
+    d = Dist(abi.MMB_IR_DISCRETEUNIFORM)
+    d.lo, d.hi = int(a), int(b)
+    return d
+
+
 def MvNormal(mu, sigma):
     """MvNormal(mu, sigma) / MvNormal(k, sigma) (zero mean): isotropic ScalMat covariance."""
     if isinstance(mu, (int, np.integer)) and not isinstance(mu, bool):
@@ -206,7 +241,10 @@ def Sampler(params, f):
         raise ArgumentError("a node-IR Sampler closure must return rand(Normal | InverseGamma | Gamma)")
     s.traced = out.dist
     return s
-_DISCRETE = {abi.MMB_IR_BINOMIAL, abi.MMB_IR_POISSON, abi.MMB_IR_BERNOULLI}
+_DISCRETE = {abi.MMB_IR_BINOMIAL, abi.MMB_IR_POISSON, abi.MMB_IR_BERNOULLI, abi.MMB_IR_CATEGORICAL,
+             abi.MMB_IR_DISCRETEUNIFORM}
+# DGSUnivariateDistribution (dgs.jl:6-8) without the two hypergeometrics
+_DGS_FAMILIES = _DISCRETE - {abi.MMB_IR_POISSON}
 _POSITIVE = {abi.MMB_IR_INVGAMMA, abi.MMB_IR_GAMMA, abi.MMB_IR_EXPONENTIAL}
 
 
@@ -266,6 +304,16 @@ class Model(_BaseModel):
 
     # setsamplers! is checked once the node lengths are known (init_matrix)
     def setsamplers(self, samplers):
+        # DGS(["a", "b"]) updates its keys one after another (dgs.jl:61-80): one device block per node,
+        # in order, so that a block's terms are the node and that node's targets (dgs.jl:109-126 mass)
+        split = []
+        for s in samplers:
+            if s.kind == abi.MMB_SAMPLER_DGS and len(s.params) != 1:
+                from .samplers import DGS
+                split += [DGS(p) for p in s.params]
+            else:
+                split.append(s)
+        samplers = split
         for s in samplers:
             if s.kind == abi.MMB_SAMPLER_GIBBS and getattr(s, "traced", None) is None:
                 raise ArgumentError("on the node IR a Gibbs block is a traced closure: ir.Sampler(params, f) "
@@ -301,6 +349,12 @@ class Model(_BaseModel):
         if len(inits) < chains:
             raise ArgumentError("fewer initial values than chains")
         self._compile(inits[0])
+        for k in range(chains):  # sampled discrete nodes start inside their supports (they index x[T])
+            for n in self.discrete:
+                v = self._initval(inits[k], n)
+                lo, hi = self.support[n]
+                if v.size != self.lens[n] or np.any(v != np.round(v)) or np.any(v < lo) or np.any(v > hi):
+                    raise ArgumentError(f"initial value of discrete node {n} (chain {k + 1}) is outside its support")
         for k in range(1, chains):  # fixed (observed) nodes are data: equal in every chain
             for n in self.fixed:
                 if not np.array_equal(self._initval(inits[k], n), self.fixed_vals[n]):
@@ -325,9 +379,19 @@ class Model(_BaseModel):
                 raise ArgumentError(f"incompatible initial value for node : {n}")
             self.lens[n] = v.size
         self.fixed_vals = {n: self._initval(init0, n) for n in self.fixed}
-        for n in self.params:
-            if self.traced[n].fam not in _SAMPLEABLE:
-                raise ArgumentError(f"node {n}: its distribution family cannot be sampled by these samplers")
+        by_dgs = {p for s in self.samplers if s.kind == abi.MMB_SAMPLER_DGS for p in s.params}
+        for s in self.samplers:
+            for n in s.params:
+                fam = self.traced[n].fam
+                if s.kind == abi.MMB_SAMPLER_DGS:
+                    if fam not in _DGS_FAMILIES:
+                        raise ArgumentError(f"DGS: node {n} is not a Bernoulli, Binomial, Categorical or "
+                                            "DiscreteUniform node")
+                elif fam in _DISCRETE:
+                    raise ArgumentError(f"discrete node {n} cannot be sampled by {s!r}: use DGS")
+                elif fam not in _SAMPLEABLE:
+                    raise ArgumentError(f"node {n}: its distribution family cannot be sampled by these samplers")
+        self.discrete = [n for n in self.params if n in by_dgs]
         # state layout: sampled nodes in declaration order
         off = 0
         self.nodes = {}
@@ -340,7 +404,7 @@ class Model(_BaseModel):
             raise ArgumentError(f"node IR: 1..{abi.MMB_IR_MAX_VALUES} sampled values")
         for s in self.samplers:
             d = self.block_dim(s)
-            if d > 32:
+            if d > 32 and s.kind != abi.MMB_SAMPLER_DGS:  # (DGS visits its elements one by one)
                 raise ArgumentError(f"node IR: blocks of at most 32 elements (block {s.params} has {d})")
             if s.kind == abi.MMB_SAMPLER_GIBBS and d != 1:
                 raise ArgumentError(f"node IR: a Sampler closure draws one scalar node ({s.params[0]} has {d})")
@@ -504,9 +568,31 @@ class _Lowering:
             v = m.fixed_vals[e.name] if k == "fixed" else m.inputs[e.name]
             o = self.put(("v", e.name), v)
             return push(self.word(op["datas"] if ln == 1 else op["data"], o))
+        if isinstance(e, Gather) and e.idx in m.defs and e.idx in getattr(m, "discrete", ()):
+            # x[T], T a sampled discrete node: the index is state (MMB_IR_OP_VALV / _DATAV)
+            if m.lens[e.idx] != n:
+                raise ArgumentError(f"gather index {e.idx} has length {m.lens[e.idx]}, expected {n}")
+            k = self.kind(e.name)
+            if k == "logical":
+                raise ArgumentError("gather from a logical: gather its parents instead")
+            ln = self.length(Ref(e.name))
+            lo, hi = self.support_bounds(e.idx)
+            if lo < 1 or hi > ln:
+                raise ArgumentError(f"{e.name}[{e.idx}]: the support {lo}..{hi} of {e.idx} must lie in 1..{ln}")
+            refs.add(e.idx)
+            if k == "param":
+                refs.add(e.name)
+                sp2 = push(self.word(op["valv"], m.nodes[e.name].offset))
+            else:
+                if k == "fixed":
+                    self.fixed_reads.add(e.name)
+                v = m.fixed_vals[e.name] if k == "fixed" else m.inputs[e.name]
+                sp2 = push(self.word(op["datav"], self.put(("v", e.name), v)))
+            self.code.append(m.nodes[e.idx].offset)
+            return sp2
         if isinstance(e, Gather):
             if e.idx not in m.inputs:
-                raise ArgumentError(f"gather index {e.idx} must be an input (data) vector")
+                raise ArgumentError(f"gather index {e.idx} must be an input (data) vector or a sampled discrete node")
             idx = m.inputs[e.idx]
             if idx.size != n:
                 raise ArgumentError(f"gather index {e.idx} has length {idx.size}, expected {n}")
@@ -534,6 +620,40 @@ class _Lowering:
         sp = self.emit(e.a, n, sp, refs)
         self.code.append(op[e.op] << 24)
         return sp
+
+    def cat_p(self, name):
+        """The probability vector of Categorical node `name` (a constant list or a data vector), checked
+        as Distributions' isprobvec does."""
+        p = self.m.traced[name].p
+        if isinstance(p, Ref):
+            if self.kind(p.name) != "data":
+                raise ArgumentError(f"Categorical p of {name} must be a constant list or a data vector")
+            p = self.m.inputs[p.name]
+        if p.size < 1 or not np.all(np.isfinite(p)) or np.any(p < 0.0) or \
+                abs(float(p.sum()) - 1.0) > math.sqrt(np.finfo(float).eps):
+            raise ArgumentError(f"Categorical p of {name} is not a probability vector")
+        return p
+
+    def binomial_n(self, name):
+        dist, ln = self.m.traced[name], self.m.lens[name]
+        nn = self.host_value(dist.params[0], ln)
+        if nn is None:
+            raise ArgumentError(f"Binomial n of {name} must be data")
+        return nn
+
+    def support_bounds(self, name):
+        """(lo, hi) of discrete node `name` over all its elements (integers)."""
+        dist = self.m.traced[name]
+        if dist.fam == abi.MMB_IR_BERNOULLI:
+            return 0, 1
+        if dist.fam == abi.MMB_IR_BINOMIAL:
+            nn = self.binomial_n(name)
+            if np.any(nn != np.round(nn)) or nn.min() < 0:
+                raise ArgumentError(f"Binomial n of {name} must be non-negative integers")
+            return 0, int(nn.max())
+        if dist.fam == abi.MMB_IR_CATEGORICAL:
+            return 1, int(self.cat_p(name).size)
+        return dist.lo, dist.hi
 
     def expr(self, e, n, refs):
         start = len(self.code)
@@ -594,6 +714,7 @@ class _Lowering:
 
     def run(self):
         m = self.m
+        m.support = {}
         ids = {n: i for i, n in enumerate(m.order)}
         nodes = (abi.IrNode * len(m.order))()
         parents = {}
@@ -623,6 +744,12 @@ class _Lowering:
                 if self.length(ps[1]) != 1:
                     raise ArgumentError(f"MvNormal sigma of {n} must be a scalar")
                 N.expr[1] = self.expr(ps[1], 1, refs)
+            elif dist.fam == abi.MMB_IR_BINOMIAL and n in m.params:
+                # sampled: n as one data word, so that the engine can check every element's support
+                nn = self.binomial_n(n)
+                N.expr[0] = len(self.code)
+                self.code += [self.word(abi.IR_OP["data"], self.put(("binn", n), nn)), 0]
+                N.expr[1] = self.expr(ps[1], ln, refs)
             else:
                 for k, p in enumerate(ps):
                     N.expr[k] = self.expr(p, ln, refs)
@@ -631,9 +758,34 @@ class _Lowering:
                 if lo is None or hi is None:
                     raise ArgumentError(f"Uniform bounds of {n} must be constants or data")
                 N.lo, N.hi = float(lo[0]), float(hi[0])
-            if dist.fam in _DISCRETE:
-                if n in m.params:
-                    raise ArgumentError(f"discrete node {n} cannot be sampled")
+            if dist.fam in _DISCRETE and n in m.params:
+                # sampled by a DGS block: the support lo..hi, at most one value per lane of the group
+                if dist.fam == abi.MMB_IR_POISSON:
+                    raise ArgumentError(f"Poisson node {n} cannot be sampled (infinite support): observed only")
+                lo, hi = self.support_bounds(n)
+                if hi - lo + 1 > abi.MMB_DGS_MAX_SUPPORT:
+                    raise ArgumentError(f"discrete node {n}: a support of {hi - lo + 1} values exceeds the "
+                                        f"{abi.MMB_DGS_MAX_SUPPORT} that DGS enumerates")
+                N.lo, N.hi = float(lo), float(hi)
+                m.support[n] = (lo, hi)
+                if dist.fam == abi.MMB_IR_BINOMIAL:
+                    nn = self.binomial_n(n)
+                    m.support[n] = (0, nn)
+                    # lchoose(n_i, k), k = 0..max n, per element (0 past n_i: off the support)
+                    N.cterm = self.put(("ct", n), [
+                        math.lgamma(a + 1) - math.lgamma(k + 1) - math.lgamma(a - k + 1) if k <= a else 0.0
+                        for a in nn for k in range(hi + 1)])
+                elif dist.fam == abi.MMB_IR_CATEGORICAL:
+                    N.cterm = self.put(("catp", n), self.cat_p(n))
+            elif dist.fam in (abi.MMB_IR_CATEGORICAL, abi.MMB_IR_DISCRETEUNIFORM):
+                lo, hi = self.support_bounds(n)
+                N.lo, N.hi = float(lo), float(hi)
+                x = m.fixed_vals[n]
+                if np.any(x != np.round(x)) or x.min() < lo or x.max() > hi:
+                    raise ArgumentError(f"{n}: observations must be integers in {lo}..{hi}")
+                if dist.fam == abi.MMB_IR_CATEGORICAL:
+                    N.cterm = self.put(("catp", n), self.cat_p(n))
+            elif dist.fam in _DISCRETE:
                 x = m.fixed_vals[n]
                 if np.any(x != np.round(x)) or x.min() < 0:
                     raise ArgumentError(f"{n}: discrete observations must be non-negative integers")

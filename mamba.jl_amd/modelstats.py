@@ -109,6 +109,11 @@ def dic_sharded(engine, model, allreduce_sum=None):
     so the partials are additive: pD = S1 / N, var(D) = (S2 - S1^2 / N) / (N - 1)."""
     red = (lambda v: np.asarray(allreduce_sum(np.asarray(v, dtype=np.float64)), dtype=np.float64)) \
         if allreduce_sum is not None else (lambda v: np.asarray(v, dtype=np.float64))
+    if getattr(model, "discrete", None):
+        # Dhat is the deviance at the posterior means (modelstats.jl:15-25), and the mean of a sampled
+        # discrete node is no point of its support: the reference's x[T] throws on a fractional index
+        raise ArgumentError("dic: the posterior mean of a sampled discrete node (" + ", ".join(model.discrete) +
+                            ") is outside its support, so the deviance at the means is undefined")
     ids = node_ids(model, model.keys("output"))
     n, K, p = engine.num_kept(), engine.K, engine.pmon
     if n < 1:

@@ -11,6 +11,8 @@ Argument meaning, defaults and validation errors follow the reference:
   HMC(params, epsilon, L[, Sigma]; dtype=:forward)            src/samplers/hmc.jl:47-65
   MALA(params, epsilon[, Sigma]; dtype=:forward)              src/samplers/mala.jl:43-58
   RWM(params, scale, proposal=Normal)                          src/samplers/rwm.jl:49-63
+  DGS(params)  -- discrete Gibbs sampling of discrete nodes      src/samplers/dgs.jl:56-80
+                  (node-IR models; no tuning, nothing adapts)
   Gibbs(params)  -- a user `Sampler(params, f)` whose f is the node's conjugate full
                     conditional (doc/tutorial/line.jl:27-45); lowered per model.
 """
@@ -87,7 +89,7 @@ class Sampler:
         return self.tuning
 
     def __repr__(self):
-        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM"}
+        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS"}
         return f"{names[self.kind]}({self.params})"
 
 
@@ -171,6 +173,15 @@ def RWM(params, scale, proposal=Normal):
     if sc.ndim != 1 or not (np.isfinite(sc).all() and (sc >= 0.0).all()):
         raise ArgumentError("scale must be a finite non-negative scalar or vector")
     return Sampler(params, abi.MMB_SAMPLER_RWM, abi.MMB_ADAPT_NONE, sc, form=form, transform=True)
+
+
+def DGS(params):
+    """DGS(params) -- dgs.jl:56-80: each element of each discrete node of `params` is drawn from its full
+    conditional, enumerated over the element's support (Bernoulli, Binomial, Categorical,
+    DiscreteUniform; at most 32 values).  Node-IR models only.  The reference updates the keys one
+    after another (dgs.jl:61-80), so a node-IR model lowers DGS(["a", "b"]) into one device block
+    per node, in order (ir.Model.setsamplers).  No tuning state."""
+    return Sampler(params, abi.MMB_SAMPLER_DGS, abi.MMB_ADAPT_NONE, None)
 
 
 def Gibbs(params):
