@@ -45,16 +45,26 @@ struct mmb_bc {
 // through.  So they return the IEEE results bit for bit (the oracle uses C sqrt and /).
 // Callers check the range and take sqrt() / division otherwise.
 __device__ __forceinline__ bool mmb_fast_range(double x) { return x >= 0x1p-700 && x <= 0x1p700; }
-__device__ __forceinline__ double mmb_sqrt_inrange(double x) {
+// The square root in two parts, for callers that go on with its half-reciprocal (mmb_rcp_seeded).
+// The prefix is rsq + one Goldschmidt step: g ~ sqrt(x), h ~ 1 / (2 sqrt(x)), h good to about
+// 2^-52; the finish takes the two residual corrections.  mmb_sqrt_inrange is the two back to back.
+__device__ __forceinline__ void mmb_sqrt_prefix(double x, double* gp, double* hp) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
   const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
+  *gp = fma(g, r, g);
+  *hp = fma(h, r, h);
+}
+__device__ __forceinline__ double mmb_sqrt_finish(double x, double g, double h) {
   double d = fma(-g, g, x);
   g = fma(d, h, g);
   d = fma(-g, g, x);
   return fma(d, h, g);
+}
+__device__ __forceinline__ double mmb_sqrt_inrange(double x) {
+  double g, h;
+  mmb_sqrt_prefix(x, &g, &h);
+  return mmb_sqrt_finish(x, g, h);
 }
 __device__ __forceinline__ double mmb_rcp_inrange(double y) {
   double r = __builtin_amdgcn_rcp(y);
@@ -65,14 +75,33 @@ __device__ __forceinline__ double mmb_rcp_inrange(double y) {
   e = fma(-y, r, 1.0);
   return fma(e, r, r);
 }
-// Both for the pivoted Cholesky: s = sqrt(x), r = 1.0 / s.  (A shorter reciprocal seeded by
-// the square root's Goldschmidt half-reciprocal, one Newton step and the final correction,
-// matched on 2^32 random samples but returned wrong last bits near binade boundaries --
-// x within 8 ulps of a power of two, sqrt(x) with an all-ones significand -- in the directed
-// set of tools/sqrt_rcp_check.hip; the rcp-seeded sequence matches there as well.)
+// Both for the pivoted Cholesky: s = sqrt(x), r = 1.0 / s, IEEE on the whole fast range (the
+// checked factorization pass and line_amm.hip use it).
 __device__ __forceinline__ void mmb_sqrt_rcp_inrange(double x, double* s, double* rcp) {
   *s = mmb_sqrt_inrange(x);
   *rcp = mmb_rcp_inrange(*s);
+}
+// The shorter reciprocal of the optimistic factorization pass: 1.0 / s for s = sqrt(x) just
+// finished by mmb_sqrt_finish, seeded by the prefix's half-reciprocal h instead of v_rcp_f64.
+// 2 h is 1 / s to a few 2^-52, so one Newton step leaves r within 2^-100 of 1 / s before its
+// rounding -- a faithful estimate -- and the final correction fma(e, r, r) rounds a faithful
+// estimate correctly unless s has an all-ones significand (Markstein's exception; then e is
+// about an ulp of 1.0 and the correction can land one ulp off).  s is all ones exactly for
+// x = 4^k (1 - n 2^-53), n = 1, 2.  The sequence is therefore 1.0 / s bit for bit except on
+// those x, which mmb_rcp_seeded_doubt covers generously: any x whose significand lies within
+// 64 ulps of a binade boundary, 129 of 2^52 significands (< 2^-44).  The caller sends such x
+// to a path that divides (pchol32: the checked pass).  tools/sqrt_rcp_check.hip compares both
+// against sqrt() and 1.0 / sqrt() on the device, tests/test_pivot_rcp_host.py the Newton step
+// and correction alone with seeds up to 3 ulps off.
+__device__ __forceinline__ double mmb_rcp_seeded(double s, double h) {
+  double r = h + h;  // exact
+  double e = fma(-s, r, 1.0);
+  r = fma(r, e, r);
+  e = fma(-s, r, 1.0);
+  return fma(e, r, r);
+}
+__device__ __forceinline__ bool mmb_rcp_seeded_doubt(double x) {
+  return ((mmb_d2u(x) + 64ull) & 0xFFFFFFFFFFFFFull) <= 128ull;
 }
 
 // AMM factorization counters per chain (mmb_amm_stats fields; 64-bit: a chain adds up to d = 30 to

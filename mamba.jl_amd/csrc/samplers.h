@@ -499,7 +499,9 @@ struct Smp {
   // pchol for 32-lane groups with one row per lane (rats), same results as pchol():
   // * the pivot lane computes sqrt / reciprocal of its remaining diagonal by the in-range
   //   sequences of device.h (bit-identical to sqrt() and 1.0 / x there) and publishes the
-  //   reciprocal through LDS together with its factor row;
+  //   reciprocal through LDS together with its factor row.  In the optimistic pass it takes
+  //   the reciprocal from the root's half-reciprocal (mmb_rcp_seeded: no v_rcp_f64, one Newton
+  //   step less), and the last step publishes no reciprocal;
   // * the search reduces the high words of the positive candidates as int32 (one DPP
   //   max per stage); a unique maximal high word is the unique maximum.  High-word ties
   //   and NaN candidates go to pivot_exact (dpstf2's first maximum in position order).
@@ -623,7 +625,9 @@ struct Smp {
     // Returns whether the pass has to be redone (the checked pass: never).
     auto pass = [&](auto checked_c) __attribute__((always_inline)) -> bool {
       constexpr bool CHECKED = decltype(checked_c)::value;
-      double apiv = 1.0;  // optimistic pass: this lane's candidate when it was taken as the pivot
+      // optimistic pass: this lane's candidate when it was taken as the pivot (until then a value
+      // the post-loop check passes)
+      double apiv = 1.5;
       double inf_s = __builtin_inf();
       asm volatile("" : "+s"(inf_s));  // +inf in an SGPR pair: one v_mov_b64 per pivot
 #pragma unroll
@@ -685,14 +689,26 @@ struct Smp {
                 for (int k = 0; k + 1 < j; k += 2) *(double2*)(prow + k) = make_double2(Lrow[k], Lrow[k + 1]);
                 if (j & 1) prow[j - 1] = Lrow[j - 1];
               }
-              double ajj, rinv;
-              if (fast) {
-                mmb_sqrt_rcp_inrange(dl, &ajj, &rinv);  // IEEE results in the fast range (device.h)
+              double ajj;
+              if constexpr (!CHECKED) {
+                // IEEE sqrt in the fast range; the reciprocal seeded from its half-reciprocal is
+                // 1.0 / ajj except on the candidates the post-loop check sends to the checked pass
+                // (device.h).  Running the prefix on every lane ahead of the search, in the DPP
+                // stages' wait states, was measured slower than this.
+                double sg, sh;
+                mmb_sqrt_prefix(dl, &sg, &sh);
+                ajj = mmb_sqrt_finish(dl, sg, sh);
+                if (j + 1 < d) prow[RI] = mmb_rcp_seeded(ajj, sh);  // (last step: no readers)
               } else {
-                ajj = sqrt(dl);
-                rinv = 1.0 / ajj;
+                double rinv;
+                if (fast) {
+                  mmb_sqrt_rcp_inrange(dl, &ajj, &rinv);  // IEEE results in the fast range (device.h)
+                } else {
+                  ajj = sqrt(dl);
+                  rinv = 1.0 / ajj;
+                }
+                prow[RI] = rinv;
               }
-              prow[RI] = rinv;
               Lrow[j] = ajj;
               pe = j;
               work = inf_s;
@@ -740,6 +756,8 @@ struct Smp {
         // What the optimistic choices could get wrong, checked once after the loop:
         // * a pivot outside the in-range square root's domain [2^-700, 2^700] -- a tiny or zero
         //   maximum, a huge or +inf one, a positive NaN key (it would have been the maximum);
+        // * a pivot whose seeded reciprocal may differ from 1.0 / ajj (device.h mmb_rcp_seeded_doubt:
+        //   a significand within 64 ulps of a binade boundary);
         // * a NaN candidate that never became a pivot (dpstf2 may stop on it; its work stays NaN
         //   to the end because NaN + x = NaN and only pivots reset work);
         // * a high-word tie: every lane holding the maximal key became a pivot at that step, so
@@ -747,7 +765,7 @@ struct Smp {
         //   taken once when exact: done == max_pe + 1).
         // On a tie the rows the pass computed after it are garbage; the redo replaces them.
         done = work == inf_s;
-        const bool inr = apiv >= 0x1p-700 && apiv <= 0x1p700;
+        const bool inr = apiv >= 0x1p-700 && apiv <= 0x1p700 && !mmb_rcp_seeded_doubt(apiv);
         uint64_t need = __ballot(inb && (done ? !inr : isnan(diag0 - work)));
         const uint64_t dn = __ballot(done && inb);
         const int mpe = gmax_i32((done && inb) ? pe : -1);
