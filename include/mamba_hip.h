@@ -87,8 +87,10 @@ typedef enum {
   MMB_SAMPLER_HMC = 6,   /* src/samplers/hmc.jl:47-65 */
   MMB_SAMPLER_MALA = 7,  /* src/samplers/mala.jl:43-58 */
   MMB_SAMPLER_RWM = 8,   /* src/samplers/rwm.jl:49-71 (additive: the ABI version is unchanged) */
-  MMB_SAMPLER_DGS = 9    /* src/samplers/dgs.jl:56-126: discrete Gibbs sampling of one discrete node-IR node
+  MMB_SAMPLER_DGS = 9,   /* src/samplers/dgs.jl:56-126: discrete Gibbs sampling of one discrete node-IR node
                             (additive: the ABI version is unchanged) */
+  MMB_SAMPLER_SLICESIMPLEX = 10 /* src/samplers/slicesimplex.jl:24-122: slice sampling of one Dirichlet node-IR node
+                                   on its simplex; mmb_block_spec.scale in (0, 1], no tune state (additive too) */
 } mmb_sampler_kind;
 
 typedef enum { MMB_ADAPT_ALL = 0, MMB_ADAPT_BURNIN = 1, MMB_ADAPT_NONE = 2 } mmb_adapt;
@@ -123,7 +125,7 @@ typedef struct {
   int32_t batchsize;                       /* AMWG batchsize (default 50) */
   double target;                           /* AMWG target (0.44) / NUTS target (0.6) */
   double beta;                             /* AMM beta (0.05) */
-  double scale;                            /* AMM scale (2.38) */
+  double scale;                            /* AMM scale (2.38); SliceSimplex scale in (0, 1] */
   int32_t dim;                             /* unlisted block length (checked by mmb_create) */
   int32_t ntuning;                         /* length of `tuning` */
   const double* tuning;                    /* AMWG sigma[dim] | Slice width[dim] | RWM scale[dim] | AMM Sigma[dim*dim] col-major
@@ -167,8 +169,19 @@ typedef enum {
   MMB_IR_LOGICAL = 11,    /* Logical: expr[0] is the value (monitored logicals) */
   MMB_IR_CATEGORICAL = 12,     /* Categorical(p), support 1..K: no parameter expression; cterm = pool offset of
                                   the K probabilities (shared by every element), lo = 1, hi = K */
-  MMB_IR_DISCRETEUNIFORM = 13  /* DiscreteUniform(a, b), constant integer bounds lo / hi */
+  MMB_IR_DISCRETEUNIFORM = 13, /* DiscreteUniform(a, b), constant integer bounds lo / hi */
+  MMB_IR_DIRICHLET = 14        /* Dirichlet(alpha): one node is one distribution of 2 <= len <= 32 elements, a
+                                  node-level density; no parameter expression; cterm = pool offset of
+                                  alpha[len], then lmnB = sum lgamma(alpha_i) - lgamma(sum alpha_i) */
 } mmb_ir_family;
+/* A sampled Dirichlet node is updated by a SliceSimplex block only, and such a block holds exactly one
+ * Dirichlet node.  Its support is the probability vectors: every x_i >= 0 and |sum x - 1| <=
+ * MMB_SIMPLEX_TOL; off it the log density is -Inf.
+ * Categorical(P) with P a sampled Dirichlet node reads its probabilities from the chain state:
+ * cterm = MMB_IR_CAT_STATE(off) <= -2, off = the first state slot of P, and hi = len(P). */
+#define MMB_SIMPLEX_TOL 1e-8
+#define MMB_SIMPLEX_MAX 32
+#define MMB_IR_CAT_STATE(off) (-2 - (off))
 /* A sampled discrete node (Bernoulli, Binomial, Categorical, DiscreteUniform) is updated by a DGS block only,
  * and a DGS block holds exactly one such node; its support is the integers lo..hi (Binomial: 0..n_i of
  * element i), at most MMB_DGS_MAX_SUPPORT values.  Off the support its log density is -Inf. */
@@ -202,7 +215,9 @@ typedef struct {
   int32_t expr[3];   /* code offsets of the distribution parameters (Distributions order), -1 none */
   int32_t cterm;     /* pool offset of a per-element constant (log binomial coefficient,
                         -lgamma(k+1)) or -1.  Sampled Binomial: a table of lchoose(n_i, k), k = 0..hi, per
-                        element i, at cterm + i (hi + 1) + k (0 where k > n_i).  Categorical: the K probabilities */
+                        element i, at cterm + i (hi + 1) + k (0 where k > n_i).  Categorical: the K probabilities,
+                        or MMB_IR_CAT_STATE(off): they are state slots off .. off + K - 1 (a sampled Dirichlet
+                        node).  Dirichlet: alpha[len], lmnB */
   double lo, hi;     /* Uniform bounds; sampled discrete nodes and Categorical / DiscreteUniform: the support */
 } mmb_ir_node;
 

@@ -18,7 +18,7 @@ from .modelstats import predict, predict_moments_sharded, predict_sharded, predi
 from .mcmc import Chains, Engine, mcmc, mcmc_restart, read, write  # noqa: F401
 from .model import line, logistic, rats  # noqa: F401
 from .samplers import (AMM, AMWG, DGS, HMC, MALA, NUTS, RWM, ArgumentError, Gibbs, Multivariate, Sampler,  # noqa: F401
-                       Slice, Univariate)
+                       Slice, SliceSimplex, Univariate)
 from .samplers import (Biweight, Cosine, Epanechnikov, Normal, SymTriangularDist, SymUniform,  # noqa: F401
                        Triweight)
 

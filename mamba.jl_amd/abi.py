@@ -17,6 +17,9 @@ MMB_SAMPLER_HMC, MMB_SAMPLER_MALA = 6, 7
 MMB_SAMPLER_RWM = 8  # additive: MMB_ABI_VERSION is unchanged
 MMB_SAMPLER_DGS = 9  # additive too
 MMB_DGS_MAX_SUPPORT = 32
+MMB_SAMPLER_SLICESIMPLEX = 10  # additive too
+MMB_SIMPLEX_MAX, MMB_SIMPLEX_TOL = 32, 1e-8
+MMB_SUB_SIMPLEX = 6  # csrc/mmb_math.h: the Dirichlet(1, ..., 1) draws of a SliceSimplex block
 (MMB_RWM_NORMAL, MMB_RWM_SYMUNIFORM, MMB_RWM_SYMTRIANGULAR, MMB_RWM_EPANECHNIKOV, MMB_RWM_BIWEIGHT,
  MMB_RWM_TRIWEIGHT, MMB_RWM_COSINE) = range(7)
 MMB_ABI_VERSION = 10
@@ -37,6 +40,7 @@ MMB_LOGISTIC_BETA = 0
 (MMB_IR_NORMAL, MMB_IR_ISONORMAL, MMB_IR_INVGAMMA, MMB_IR_GAMMA, MMB_IR_EXPONENTIAL, MMB_IR_UNIFORM, MMB_IR_BETA,
  MMB_IR_BINOMIAL, MMB_IR_POISSON, MMB_IR_BERNOULLI, MMB_IR_LOGICAL) = range(1, 12)
 MMB_IR_CATEGORICAL, MMB_IR_DISCRETEUNIFORM = 12, 13
+MMB_IR_DIRICHLET = 14
 IR_OP = {"end": 0, "const": 1, "val": 2, "vali": 3, "valg": 4, "data": 5, "datas": 6, "valv": 7, "datav": 8,
          "+": 16, "-": 17, "*": 18, "/": 19,
          "neg": 32, "exp": 33, "log": 34, "sqrt": 35, "invlogit": 36, "logit": 37, "abs": 38}

@@ -192,6 +192,8 @@ struct SweepArgs {
   int32_t amwg_probe;    // MMB_AMWG_PROBE=1 (tests only): near-threshold AMWG accept uniforms
                          // (mmb_math.h mmb_amwg_probe_factor)
   int32_t ir_npool;      // node IR: entries of ir_pool (ir.h ev clamps a state-valued pool index to it)
+  int32_t ir_ssx;        // node IR: doubles of the SliceSimplex vertex rows at the end of a chain's LDS
+                         // (32 x the widest such block; 0 without one: the layout is then unchanged)
 };
 
 // Wavefront pairing (sweep.hip order_chains_kernel): classes from the first MMB_ORDER_BLOCKS AMM
@@ -224,6 +226,12 @@ __device__ __forceinline__ void grp_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// whether p holds on any lane of this lane's 32-lane group (a lane that is switched off counts as false)
+__device__ __forceinline__ bool grp_any(bool p) {
+  const unsigned long long m = __ballot(p);
+  return (uint32_t)((threadIdx.x & 32) != 0 ? (m >> 32) : m) != 0u;
 }
 
 // ---- cross-lane primitives for 32-lane groups: DPP / permlane (no LDS round trip) ----

@@ -185,6 +185,7 @@ struct mmb_engine {
   hipFunction_t jit_fn = nullptr;
   bool ir_noprop = false;  // specialised AMM + Gibbs kernel: no candidate copy of the state (ir.h NOPROP)
   int ir_stack_dbl = 0;    // specialised kernel's expression-stack LDS doubles
+  int ssx_kmax = 0;        // elements of the widest SliceSimplex block (0: none)
   std::string jit_info;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -222,11 +223,12 @@ static int node_dim(const mmb_model_spec& s, const mmb_ir_model* ir, int node, b
   bool pos = false;
   int d = -1;
   if (s.model == MMB_MODEL_IR) {
-    // sampled nodes only: not fixed, not Logical; a discrete family only where a DGS block samples it
-    // (ir_validate checks that it is one)
+    // sampled nodes only: not fixed, not Logical; a discrete family only where a DGS block samples it,
+    // a Dirichlet node only where a SliceSimplex block does (ir_validate and create_impl check both)
     if (ir && node >= 0 && node < ir->nnodes) {
       const mmb_ir_node& n = ir->nodes[node];
-      const bool ok = !n.fixed && ((n.family >= MMB_IR_NORMAL && n.family <= MMB_IR_BETA) || ir_dgs_family(n.family));
+      const bool ok = !n.fixed && ((n.family >= MMB_IR_NORMAL && n.family <= MMB_IR_BETA) || ir_dgs_family(n.family) ||
+                                   n.family == MMB_IR_DIRICHLET);
       d = ok ? n.len : -1;
     }
   } else if (s.model == MMB_MODEL_LINE) {
@@ -342,6 +344,7 @@ static int tune_len_of(int kind, int d) {
     case MMB_SAMPLER_MALA: return 1;  // [epsilon]        (MALATune, mala.jl:5-9)
     case MMB_SAMPLER_RWM: return d;   // scale[d]         (RWMTune, rwm.jl:5-9)
     case MMB_SAMPLER_DGS: return 0;   // no tuning state  (DGSTune holds only the mass function, dgs.jl:12-26)
+    case MMB_SAMPLER_SLICESIMPLEX: return 0;  // none either (SliceSimplexTune: logf and the constant scale)
     default: return 0;
   }
 }
@@ -622,10 +625,37 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
                       "DiscreteUniform node", b);
         }
         break;
+      case MMB_SAMPLER_SLICESIMPLEX:  // slicesimplex.jl:24-58: one Dirichlet node per block (the host splits the keys)
+        if (e->model != MMB_MODEL_IR) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: SliceSimplex samples Dirichlet nodes of node-IR models only", b);
+        }
+        if (s.nnodes != 1 || ir->nodes[s.nodes[0]].family != MMB_IR_DIRICHLET || d < 2 || d > MMB_SIMPLEX_MAX) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: a SliceSimplex block holds one Dirichlet node of 2..%d elements", b,
+                      MMB_SIMPLEX_MAX);
+        }
+        if (!(s.scale > 0.0 && s.scale <= 1.0)) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: scale is not in (0, 1]", b);
+        }
+        if (s.transform != 0) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: SliceSimplex moves on the simplex itself (transform = 0)", b);
+        }
+        e->ssx_kmax = std::max(e->ssx_kmax, d);
+        break;
       default:
         delete e;
         return fail(nullptr, MMB_E_ARG, "unknown sampler kind %d", s.sampler);
     }
+    if (e->model == MMB_MODEL_IR && s.sampler != MMB_SAMPLER_SLICESIMPLEX)
+      for (int a = 0; a < s.nnodes; ++a)
+        if (ir->nodes[s.nodes[a]].family == MMB_IR_DIRICHLET) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: Dirichlet node %d can be sampled by a SliceSimplex block only", b,
+                      s.nodes[a]);
+        }
     if (e->model == MMB_MODEL_IR && s.sampler != MMB_SAMPLER_DGS)
       for (int a = 0; a < s.nnodes; ++a)
         if (ir_dgs_family(ir->nodes[s.nodes[a]].family)) {
@@ -772,7 +802,7 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
   int depth = 0;
   for (int n = 0; n < ir->nnodes; ++n) {
     const mmb_ir_node& N = ir->nodes[n];
-    if (N.family < MMB_IR_NORMAL || N.family > MMB_IR_DISCRETEUNIFORM || N.len < 1)
+    if (N.family < MMB_IR_NORMAL || N.family > MMB_IR_DIRICHLET || N.len < 1)
       return fail(nullptr, MMB_E_ARG, "node IR: node %d has a bad family or length", n);
     if (N.family != MMB_IR_LOGICAL) {
       const int64_t end = (int64_t)N.off + N.len;
@@ -806,7 +836,41 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
           (N.lo != 0.0 || (N.family == MMB_IR_BERNOULLI && N.hi != 1.0)))
         return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d has a bad support", n);
     }
-    {  // constant table: per element; sampled Binomial (element, value); Categorical K probabilities
+    if (N.family == MMB_IR_DIRICHLET) {
+      // one Dirichlet per node, an element per lane; alpha[len] > 0 and lmnB in the pool.  A sampled one
+      // is in SliceSimplex blocks only (one node each: create_impl), and in at least one
+      if (N.len < 2 || N.len > MMB_SIMPLEX_MAX)
+        return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d needs 2..%d elements", n, MMB_SIMPLEX_MAX);
+      if (N.cterm < 0 || (int64_t)N.cterm + N.len + 1 > ir->npool)
+        return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d needs alpha[len] and lmnB in the pool", n);
+      for (int i = 0; i < N.len; ++i)
+        if (!(ir->pool[N.cterm + i] > 0.0 && std::isfinite(ir->pool[N.cterm + i])))
+          return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d: alpha[%d] must be positive", n, i);
+      if (!std::isfinite(ir->pool[N.cterm + N.len]))
+        return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d: lmnB is not finite", n);
+      if (!N.fixed) {
+        bool in_ssx = false;
+        for (int b = 0; b < spec->nblocks; ++b)
+          for (int a = 0; a < spec->blocks[b].nnodes && a < MMB_MAX_NODES_PER_BLOCK; ++a)
+            if (spec->blocks[b].nodes[a] == n) {
+              if (spec->blocks[b].sampler != MMB_SAMPLER_SLICESIMPLEX)
+                return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d can be sampled by a SliceSimplex block only", n);
+              in_ssx = true;
+            }
+        if (!in_ssx) return fail(nullptr, MMB_E_ARG, "node IR: sampled Dirichlet node %d is in no SliceSimplex block", n);
+      }
+    } else if (mmb_ir_cat_state(N.family, N.cterm) >= 0) {
+      // Categorical(P): the K = hi probabilities are the state slots of one sampled Dirichlet node of length K
+      const int po = mmb_ir_cat_state(N.family, N.cterm);
+      bool ok = false;
+      for (int q = 0; q < ir->nnodes; ++q) {
+        const mmb_ir_node& Q = ir->nodes[q];
+        if (!Q.fixed && Q.family == MMB_IR_DIRICHLET && Q.off == po && (double)Q.len == N.hi) ok = true;
+      }
+      if (!ok)
+        return fail(nullptr, MMB_E_ARG, "node IR: Categorical node %d: its probabilities must be the slots of one "
+                    "sampled Dirichlet node of length K", n);
+    } else {  // constant table: per element; sampled Binomial (element, value); Categorical K probabilities
       int64_t nct = N.len;
       if (N.family == MMB_IR_CATEGORICAL) nct = (int64_t)N.hi;
       else if (N.family == MMB_IR_BINOMIAL && dgs) nct = (int64_t)N.len * ((int64_t)N.hi + 1);
@@ -832,7 +896,8 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
                       (int)N.hi);
       }
     }
-    const int nexpr = N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM ? 0
+    const int nexpr = N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM ||
+                              N.family == MMB_IR_DIRICHLET ? 0
                       : N.family == MMB_IR_LOGICAL || N.family == MMB_IR_EXPONENTIAL || N.family == MMB_IR_POISSON ||
                               N.family == MMB_IR_BERNOULLI ? 1 : 2;
     for (int k = 0; k < 3; ++k) {
@@ -859,6 +924,17 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
         return fail(nullptr, MMB_E_ARG, "node IR: block %d term %d invalid", b, t);
     if (spec->blocks[b].sampler == MMB_SAMPLER_DGS && B.term[0] != spec->blocks[b].nodes[0])
       return fail(nullptr, MMB_E_ARG, "node IR: DGS block %d: its terms are its node, then the node's targets", b);
+    if (spec->blocks[b].sampler == MMB_SAMPLER_SLICESIMPLEX && B.term[0] != spec->blocks[b].nodes[0])
+      return fail(nullptr, MMB_E_ARG, "node IR: SliceSimplex block %d: its terms are its node, then the node's targets", b);
+    // a Dirichlet node has no sampled parent and a state-read Categorical only its P: they are terms of
+    // SliceSimplex and DGS blocks alone, and only those blocks' log densities know them (ir.h elem_lp<SX>)
+    if (spec->blocks[b].sampler != MMB_SAMPLER_SLICESIMPLEX && spec->blocks[b].sampler != MMB_SAMPLER_DGS)
+      for (int t = 0; t < B.nterms; ++t) {
+        const mmb_ir_node& Q = ir->nodes[B.term[t]];
+        if (Q.family == MMB_IR_DIRICHLET || mmb_ir_cat_state(Q.family, Q.cterm) >= 0)
+          return fail(nullptr, MMB_E_ARG, "node IR: block %d term %d: a Dirichlet node or a Categorical that reads one "
+                      "is a term of SliceSimplex and DGS blocks only", b, t);
+      }
     if (!gibbs) {
       if (B.gibbs_family != 0) return fail(nullptr, MMB_E_ARG, "node IR: block %d is not a Gibbs block", b);
       continue;
@@ -906,6 +982,20 @@ static void ir_jit_params(const mmb_model_spec* spec, const mmb_ir_model* ir, un
 // state-indexed leaves VALV / DATAV, which only such schemes hold: it declines those schemes whole
 static const char* const kJitNoDgs = "the specialised kernel declines schemes with DGS blocks: sampled discrete "
                                      "nodes and state-indexed gathers are not generated";
+// Nor for SliceSimplex blocks, the Dirichlet density or a Categorical that reads its probabilities
+// from the state
+static const char* const kJitNoSimplex = "the specialised kernel declines schemes with SliceSimplex blocks and "
+                                         "models with a Dirichlet node or a Categorical that reads a sampled P: "
+                                         "they are not generated";
+// why the generator declines the scheme (null: it does not)
+static const char* ir_jit_declined(unsigned kinds, const mmb_ir_model* ir) {
+  if (kinds & (1u << MMB_SAMPLER_SLICESIMPLEX)) return kJitNoSimplex;
+  for (int n = 0; n < ir->nnodes; ++n)
+    if (ir->nodes[n].family == MMB_IR_DIRICHLET || mmb_ir_cat_state(ir->nodes[n].family, ir->nodes[n].cterm) >= 0)
+      return kJitNoSimplex;
+  if (kinds & (1u << MMB_SAMPLER_DGS)) return kJitNoDgs;
+  return nullptr;
+}
 
 // The specialised kernel of a node-IR engine (ir_jit.cpp); on any failure the interpreter
 // kernel runs (jit_info says why).  MMB_IR_JIT=0 selects the interpreter.
@@ -918,8 +1008,8 @@ static void ir_jit_setup(mmb_engine* e, const mmb_model_spec* spec, const mmb_ir
   unsigned kinds = 0;
   int dmax = 0;
   ir_jit_params(spec, ir, &kinds, &dmax);
-  if (kinds & (1u << MMB_SAMPLER_DGS)) {
-    e->jit_info = std::string("interpreter (") + kJitNoDgs + ")";
+  if (const char* why = ir_jit_declined(kinds, ir)) {
+    e->jit_info = std::string("interpreter (") + why + ")";
     return;
   }
   std::vector<char> code;
@@ -963,6 +1053,20 @@ int mmb_create_ir(const mmb_model_spec* spec, const mmb_ir_model* ir, int device
   rc = create_impl(spec, ir, device, out);
   if (rc) return rc;
   ir_jit_setup(*out, spec, ir);
+  if ((*out)->ssx_kmax > 0) {
+    // SliceSimplex schemes run the interpreter with the vertex rows appended to each chain's LDS
+    // (fill_args): four chains per 128-thread workgroup must fit the 64 KiB of a launch
+    const mmb_engine* e = *out;
+    const int G = Mdl<MMB_MODEL_IR>::G;
+    const int64_t per_chain = ((e->kinds & (1u << MMB_SAMPLER_AMM)) ? e->TP + 4 * Mdl<MMB_MODEL_IR>::DP + 2 : 0) +
+                              2 * (int64_t)e->VS + (int64_t)(e->ir_stack + 1) * G + (int64_t)e->ssx_kmax * G;
+    if (per_chain * (128 / G) * (int64_t)sizeof(double) > 65536) {
+      mmb_destroy(*out);
+      *out = nullptr;
+      return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: the scheme's LDS (%lld doubles per chain with the SliceSimplex "
+                  "vertex rows) exceeds a workgroup's 64 KiB", (long long)per_chain);
+    }
+  }
   return 0;
 }
 
@@ -973,9 +1077,9 @@ int mmb_ir_jit_prebuild(const mmb_model_spec* spec, const mmb_ir_model* ir, char
   unsigned kinds = 0;
   int dmax = 0;
   ir_jit_params(spec, ir, &kinds, &dmax);
-  if (kinds & (1u << MMB_SAMPLER_DGS)) {
-    if (info && n > 0) snprintf(info, (size_t)n, "%s", kJitNoDgs);
-    return fail(nullptr, MMB_E_UNSUPPORTED, "%s", kJitNoDgs);
+  if (const char* why = ir_jit_declined(kinds, ir)) {
+    if (info && n > 0) snprintf(info, (size_t)n, "%s", why);
+    return fail(nullptr, MMB_E_UNSUPPORTED, "%s", why);
   }
   std::vector<char> code;
   std::string msg;
@@ -991,7 +1095,7 @@ int mmb_ir_jit_source_text(const mmb_model_spec* spec, const mmb_ir_model* ir, c
   unsigned kinds = 0;
   int dmax = 0;
   ir_jit_params(spec, ir, &kinds, &dmax);
-  if (kinds & (1u << MMB_SAMPLER_DGS)) return fail(nullptr, MMB_E_UNSUPPORTED, "%s", kJitNoDgs);
+  if (const char* why = ir_jit_declined(kinds, ir)) return fail(nullptr, MMB_E_UNSUPPORTED, "%s", why);
   const std::string src = mmb_ir_jit_source(*spec, *ir, kinds, dmax);
   if (buf && n > 0) snprintf(buf, (size_t)n, "%s", src.c_str());
   return (int)std::min<size_t>(src.size(), (size_t)INT32_MAX);
@@ -1241,6 +1345,25 @@ int mmb_set_values(mmb_engine* e, const double* values) {
         }
     }
   }
+  if (e->model == MMB_MODEL_IR && (e->kinds & (1u << MMB_SAMPLER_SLICESIMPLEX))) {
+    // sampled Dirichlet nodes: a probability vector (validatesimplex, sampler.jl:80-82; the support of
+    // ir_math.h mmb_ir_dirichlet_lp), so that a SliceSimplex update starts inside its first simplex
+    for (const mmb_ir_node& N : e->ir_nodes) {
+      if (N.fixed || N.family != MMB_IR_DIRICHLET) continue;
+      for (int64_t k = 0; k < e->K; ++k) {
+        double sum = 0.0;
+        bool neg = false;
+        for (int i = 0; i < N.len; ++i) {
+          const double x = values[k * e->P + N.off + i];
+          sum += x;
+          neg = neg || !(x >= 0.0);
+        }
+        if (neg || !(std::fabs(sum - 1.0) <= MMB_SIMPLEX_TOL))
+          return fail(e, MMB_E_ARG, "chain %lld: variate is not a probability vector (Dirichlet node at value slot %d)",
+                      (long long)k, N.off);
+      }
+    }
+  }
   ++e->xepoch;
   std::vector<double> h((size_t)e->K * e->VS);
   for (int64_t k = 0; k < e->K; ++k) to_device_layout(e, values + k * e->P, h.data() + k * e->VS);
@@ -1484,6 +1607,9 @@ static void fill_args(const mmb_engine* e, SweepArgs& A) {
     A.ir_amm = (e->kinds & (1u << MMB_SAMPLER_AMM)) ? (int32_t)(e->TP + 4 * Mdl<MMB_MODEL_IR>::DP + 2) : 0;
     A.ir_lds = A.ir_amm + (e->ir_noprop ? 1 : 2) * e->VS +
                (e->jit_fn ? e->ir_stack_dbl : (e->ir_stack + 1) * Mdl<MMB_MODEL_IR>::G);
+    // SliceSimplex vertex rows (samplers.h slice_simplex), last, so that every other scheme's layout stays
+    A.ir_ssx = e->ssx_kmax * Mdl<MMB_MODEL_IR>::G;
+    A.ir_lds += A.ir_ssx;
   } else if (e->model == MMB_MODEL_RATS) {
     double s = 0.0;
     for (int i = 0; i < 5; ++i) s += e->x[i];
@@ -2575,6 +2701,8 @@ static int ms_plan(mmb_engine* e, int nnodes, const int32_t* nodes, bool need_dr
     const mmb_ir_node& N = e->ir_nodes[nid];
     if (sampled(N)) need[nid] = 1;
     std::vector<int> slots;
+    if (const int po = mmb_ir_cat_state(N.family, N.cterm); po >= 0)  // Categorical(P) reads P's slots
+      for (int i = 0; i < (int)N.hi; ++i) slots.push_back(po + i);
     for (int k = 0; k < 3; ++k) {
       if (N.expr[k] < 0) continue;
       const int ne = (N.family == MMB_IR_ISONORMAL && k == 1) ? 1 : N.len;
@@ -2716,9 +2844,9 @@ static int pr_plan(mmb_engine* e, int nnodes, const int32_t* nodes, PrPlan& pl) 
   for (int a = 0; a < nnodes; ++a) {
     const mmb_ir_node& N = e->ir_nodes[nodes[a]];
     if (!N.fixed) return fail(e, MMB_E_ARG, "node id %d is not an observed Stochastic node of the model", nodes[a]);
-    if (N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM)
-      return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d: Categorical and DiscreteUniform variates are not lowered",
-                  nodes[a]);
+    if (N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM || N.family == MMB_IR_DIRICHLET)
+      return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d: Categorical, DiscreteUniform and Dirichlet variates are "
+                  "not lowered", nodes[a]);
     const bool gam = N.family == MMB_IR_GAMMA || N.family == MMB_IR_INVGAMMA || N.family == MMB_IR_BETA;
     if (gam && !mmb_pr_gblock_ok(nodes[a], N.len))
       return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d (length %d) does not fit the element blocks of the "
@@ -2994,6 +3122,7 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
       case MMB_SAMPLER_MALA: s += 8.0; break;
       case MMB_SAMPLER_RWM: s += 8.0 * h.d; break;  // scale (read only)
       case MMB_SAMPLER_DGS: break;  // no tune state; the masses stay in registers (samplers.h dgs)
+      case MMB_SAMPLER_SLICESIMPLEX: break;  // no tune state; the vertex matrix lives in LDS within one update
       default: break;
     }
   }

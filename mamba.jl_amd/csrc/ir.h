@@ -8,7 +8,8 @@
 // the AMM factorization is pchol32).  LDS per chain:
 //
 //   [AMM scratch (schemes with AMM)] [cur: chain state] [prop: state + the block's
-//   candidate x] [expression stack: depth x 32 doubles]
+//   candidate x] [expression stack: depth x 32 doubles] [SliceSimplex vertex rows: 32 x the
+//   widest such block (schemes with one)]
 //
 // logpdf!(m, x, block, transform) (src/model/simulation.jl:77-90): relist x into `prop`
 // (invlink when transformed, transformdistribution.jl:6-93), then the block's terms —
@@ -166,7 +167,11 @@ struct Mdl<MMB_MODEL_IR> {
   // logpdf_sub of element i of a node at value x (distributionstruct.jl:138-140).  The constant term is
   // per element, except a sampled Binomial's (indexed by element and value) and Categorical's (its
   // probability table, indexed by value); a sampled discrete node's value is state, so its support is
-  // tested here (an observed one's was checked by the host)
+  // tested here (an observed one's was checked by the host).  SX: the caller may meet a Categorical that
+  // reads a sampled Dirichlet node's slots, or (node_lp) a Dirichlet node: these are terms of DGS and
+  // SliceSimplex blocks of schemes that hold a SliceSimplex block only (engine.cpp ir_validate), so the
+  // other kernels' logpdf! keeps the code it had
+  template <bool SX = false>
   __device__ __forceinline__ static double elem_lp(const SweepArgs& A, const mmb_ir_node& N, int i, double x,
                                                    const double* vals, double* stk, int lane, int tr) {
     const double a = N.expr[0] >= 0 ? ev(A, N.expr[0], i, vals, stk, lane) : 0.0;
@@ -175,6 +180,16 @@ struct Mdl<MMB_MODEL_IR> {
     if (N.cterm >= 0) {
       const int ci = mmb_ir_cterm_index(N.family, N.fixed, i, x, N.lo, N.hi);
       ct = ci >= 0 ? A.ir_pool[N.cterm + ci] : 0.0;
+    } else if constexpr (SX) {
+      const int po = mmb_ir_cat_state(N.family, N.cterm);
+      if (po >= 0) {
+        // Categorical(P), P a sampled Dirichlet node: p[x] is state slot po + x - 1 (the engine checked
+        // that the K = hi slots are P's; the index is clamped to them whatever x holds)
+        int ci = mmb_ir_cterm_index(N.family, N.fixed, i, x, N.lo, N.hi);
+        const int top = (int)N.hi - 1;
+        ci = ci < 0 ? 0 : (ci > top ? top : ci);
+        ct = vals[po + ci];
+      }
     }
     if (!N.fixed && (N.family == MMB_IR_BINOMIAL || N.family == MMB_IR_BERNOULLI) &&
         !mmb_ir_discrete_in(N.family, x, a, N.lo, N.hi))
@@ -183,6 +198,7 @@ struct Mdl<MMB_MODEL_IR> {
   }
 
   // logpdf(node[, transform]) (dependent.jl:207-213 -> logpdf_sub), group-uniform result
+  template <bool SX = false>
   __device__ static double node_lp(const SweepArgs& A, int n, const double* vals, double* stk,
                                    const Grp<G>& g, int tr) {
     const mmb_ir_node& N = ir_const_ref(A.ir_nodes, n);
@@ -200,8 +216,21 @@ struct Mdl<MMB_MODEL_IR> {
       g.sum2(ss, bad);
       return bad != 0.0 ? -__builtin_inf() : d_iso(N.len, sig, ss);
     }
+    if constexpr (SX) if (N.family == MMB_IR_DIRICHLET) {  // one Dirichlet(alpha) over the node's elements (ir_math.h)
+      const double* al = A.ir_pool + N.cterm;
+      double st = 0.0, sx = 0.0;
+      bool neg = false;
+      for (int i = lane; i < N.len; i += G) {
+        const double x = src[i];
+        st = st + mmb_ir_dirichlet_term(al[i], x);
+        sx = sx + x;
+        neg = neg || !(x >= 0.0);
+      }
+      g.sum2(st, sx);
+      return mmb_ir_dirichlet_lp(st, sx, grp_any(neg), al[N.len]);
+    }
     double acc = 0.0;
-    for (int i = lane; i < N.len; i += G) acc = acc + elem_lp(A, N, i, src[i], vals, stk, lane, tr);
+    for (int i = lane; i < N.len; i += G) acc = acc + elem_lp<SX>(A, N, i, src[i], vals, stk, lane, tr);
     return g.sum(acc);
   }
 
@@ -558,13 +587,36 @@ struct Mdl<MMB_MODEL_IR> {
     }
     grp_sync();
   }
+  template <bool SX = false>
   __device__ static double dgs_lp(const SweepArgs& A, const DBlock& B, const St& s, const Grp<G>& g, int e, double v) {
     const mmb_ir_block& IB = ir_const_ref(A.ir_blocks, B.ir_blk);
     const mmb_ir_node& N = ir_const_ref(s.nodes, B.nodes[0]);
-    const double own = elem_lp(A, N, e, v, s.cur, s.stk, g.lane, 0);
+    const double own = elem_lp<SX>(A, N, e, v, s.cur, s.stk, g.lane, 0);
     double lp = 0.0;
     for (int t = 1; t < IB.nterms; ++t) {
-      lp += node_lp(A, IB.term[t], s.cur, s.stk, g, 0);
+      lp += node_lp<SX>(A, IB.term[t], s.cur, s.stk, g, 0);
+      if (!isfinite(lp)) break;
+    }
+    return own + lp;
+  }
+
+  // SliceSimplex blocks (samplers.h slice_simplex; slicesimplex.jl:32-58): one sampled Dirichlet node of
+  // k = B.d <= 32 elements per block, element i on lane i.  ssx_rows: the chain's k x k vertex matrix,
+  // row i on lane i, column j at [32 j + lane]: the region the engine appends to the chain's LDS for
+  // schemes that hold such a block (A.ir_ssx doubles, after the expression stack).  ssx_logf:
+  // logpdf(d, x) + logpdf(model, node.targets) with x written into the candidate state (put), the
+  // targets in topological order with the early exit on a non-finite running sum among them (the
+  // block's term list is the node, then its targets); group-uniform.
+  __device__ __forceinline__ static double* ssx_rows(const SweepArgs& A, double* lds) {
+    return lds + (A.ir_lds - A.ir_ssx);
+  }
+  __device__ static double ssx_logf(const SweepArgs& A, const DBlock& B, const St& s, const Grp<G>& g, const double* x) {
+    put(B, s, g.lane, x, s.prop, nullptr);
+    const mmb_ir_block& IB = ir_const_ref(A.ir_blocks, B.ir_blk);
+    const double own = node_lp<true>(A, B.nodes[0], s.prop, s.stk, g, 0);
+    double lp = 0.0;
+    for (int t = 1; t < IB.nterms; ++t) {
+      lp += node_lp<true>(A, IB.term[t], s.prop, s.stk, g, 0);
       if (!isfinite(lp)) break;
     }
     return own + lp;

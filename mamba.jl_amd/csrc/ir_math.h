@@ -119,6 +119,21 @@ MMB_HD int mmb_ir_cterm_index(int fam, int fixed, int i, double x, double lo, do
   return i;
 }
 
+/* Dirichlet(alpha) (a node-level density, ir.h node_lp): element i contributes (alpha_i - 1) log x_i,
+ * exactly 0 when alpha_i == 1 (xlogy: a flat coordinate is finite at x_i = 0).  The node is in its
+ * support iff every x_i >= 0 and |sum x - 1| <= MMB_SIMPLEX_TOL (a NaN fails both); then
+ * lp = sum_i t_i - lmnB, lmnB = sum lgamma(alpha_i) - lgamma(sum alpha_i) formed by the host. */
+MMB_HD double mmb_ir_dirichlet_term(double alpha, double x) {
+  const double c = alpha - 1.0;
+  return c == 0.0 ? 0.0 : c * mmb_log(x);
+}
+MMB_HD double mmb_ir_dirichlet_lp(double st, double sx, int neg, double lmnb) {
+  if (neg || !(fabs(sx - 1.0) <= MMB_SIMPLEX_TOL)) return -__builtin_inf();
+  return st - lmnb;
+}
+/* Categorical(P), P a sampled Dirichlet node (cterm = MMB_IR_CAT_STATE(off)): the state offset of P */
+MMB_HD int mmb_ir_cat_state(int fam, int cterm) { return fam == MMB_IR_CATEGORICAL && cterm <= -2 ? -2 - cterm : -1; }
+
 MMB_HD double mmb_ir_lp(int fam, double x, double a, double b, double ct, int tr, double lo, double hi) {
   const double NINF = -__builtin_inf(), INF = __builtin_inf();
   switch (fam) {

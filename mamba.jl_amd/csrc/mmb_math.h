@@ -42,6 +42,7 @@
 #define MMB_SUB_GAMMA_U 3u  /* Marsaglia-Tsang uniforms */
 #define MMB_SUB_INIT 4u     /* nutsepsilon momentum (nuts.jl:194) */
 #define MMB_SUB_PROPOSAL 5u /* RWM's non-Normal proposal variates (symdist.h): uniform #(8k + j) for coordinate k */
+#define MMB_SUB_SIMPLEX 6u  /* SliceSimplex's Dirichlet(1, ..., 1) draws: uniform #(32r + j) for element j of draw r */
 
 #define MMB_LOG2PI 1.8378770664093454835606594728112352797
 #define MMB_TWOPI_HI 6.28318530717958623200e+00

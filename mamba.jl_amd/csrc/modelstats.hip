@@ -56,7 +56,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_ir_kernel(const SweepArgs A, co
     for (int c = grp; c < T; c += MS_GROUPS) {
       const double* vals = img + (size_t)c * M.S;
       double lp = 0.0;
-      for (int a = 0; a < M.nnodes; ++a) lp += MI::node_lp(A, M.nodes[a], vals, stk, g, 0);
+      for (int a = 0; a < M.nnodes; ++a) lp += MI::template node_lp<true>(A, M.nodes[a], vals, stk, g, 0);
       const int64_t k = k0 + c;
       if (g.lane == 0 && k < M.K) M.lp[(size_t)i * M.K + k] = lp;
     }

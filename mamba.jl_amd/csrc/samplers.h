@@ -289,6 +289,8 @@ struct Smp {
   // A psum that is not finite (a mass overflowed to +Inf, or a NaN log density) has no probability
   // vector: the reference throws inside Categorical(probs); here the element keeps the value it had
   // before the update.  u is indexed by the element, so that draws nothing out of order.
+  // SX: the kernel also holds SliceSimplex, so a target may read a sampled Dirichlet node (ir.h elem_lp)
+  template <bool SX = false>
   __device__ __forceinline__ static void dgs(const SweepArgs& A, const DBlock& B, const mmb_rng& ru, St& s,
                                              const Grp<G>& g) {
     static_assert(G == 32, "DGS keeps one mass per lane of a 32-lane group");
@@ -300,7 +302,7 @@ struct Smp {
       double mass = 0.0;
       for (int k = 0; k < n; ++k) {
         M::dgs_set(B, s, e, lo + (double)k, g.lane);
-        const double m = mmb_exp(M::dgs_lp(A, B, s, g, e, lo + (double)k));
+        const double m = mmb_exp(M::template dgs_lp<SX>(A, B, s, g, e, lo + (double)k));
         mass = g.lane == k ? m : mass;
       }
       double psum = 0.0;
@@ -323,6 +325,87 @@ struct Smp {
       }
       M::dgs_set(B, s, e, v, g.lane);
     }
+  }
+
+  // ---------------------------------------------------------------- SliceSimplex
+  // slicesimplex.jl:86-122 (sample!, makefirstsimplex, shrinksimplex) for the block's one Dirichlet node
+  // of k = B.d <= 32 elements (node-IR models; M::ssx_* in ir.h), the reference's linear solves
+  // replaced by their closed form.  Lane i owns element i and row i of the k x k
+  // vertex matrix V (LDS, column j at V[32 j + lane]: a column read touches 32 distinct banks), so
+  // the products V xb, the first simplex and the shrink are lane-local; xb_j, bc_i come from lane j
+  // by lane_value.  Every sum runs in index order from 0.0.
+  //   draw r        w_j = e_j / (e_0 + ... + e_{k-1}), e_j = -log(1 - u), u = uniform #(32 r + j) of the
+  //                 block's MMB_SUB_SIMPLEX stream: rand(Dirichlet(1, ..., 1))
+  //   p0            logf(v) + log(uniform #0 of MMB_SUB_UNIFORM)
+  //   first simplex V0 = I, columns j >= 1 moved towards column 0 by 1 - scale; V = V0 + v - V0 w (draw 0);
+  //                 bx = w: the barycentric coordinates of v in V (V w = v by construction)
+  //   candidate r   x = V xb, xb = draw r; rejected iff some x_i < 0 or > 1 (a ballot) or logf(x) < p0
+  //                 (evaluated for an in-box x only; a NaN accepts, as in the reference)
+  //   shrink        bc = xb; for every i with bc_i < bx_i (the set is fixed first), ascending, t = bc_i now:
+  //                 V[:, j] += t (V[:, i] - V[:, j]) for j != i, and both bc and bx become
+  //                 b_j / (1 - t) (j != i), (b_i - t) / (1 - t): the coordinates of x and of v in the new V
+  // After MMB_SLICE_MAX_SHRINK rejected candidates the update stops as Slice does (slice_overflow).
+  // The two chains of a wave leave the candidate loop on their own; every cross-lane step inside it
+  // (DPP sums, lane_value, the ballot) stays within the chain's own 32 lanes.  No tune state.
+  __device__ __forceinline__ static double ssx_draw(const mmb_rng& rs, uint32_t r, int k, const Grp<G>& g) {
+    const double e = g.lane < k ? -mmb_log(1.0 - mmb_uniform(&rs, 32u * r + (uint32_t)g.lane)) : 0.0;
+    double sum = 0.0;
+    for (int j = 0; j < k; ++j) sum = sum + lane_value(e, j);
+    return e / sum;
+  }
+  __device__ static void slice_simplex(const SweepArgs& A, const DBlock& B, const mmb_rng& ru, const mmb_rng& rs,
+                                       St& s, const Grp<G>& g, double* V) {
+    static_assert(G == 32 && R == 1, "SliceSimplex keeps one row of the vertex matrix per lane of a 32-lane group");
+    const int k = B.d < G ? B.d : G, lane = g.lane;
+    double v[R];
+    M::unlist(B, s, lane, v);  // (0 on the lanes past k)
+    const double p0 = M::ssx_logf(A, B, s, g, v) + mmb_log(mmb_uniform(&ru, 0u));
+    double bx = ssx_draw(rs, 0u, k, g);
+    {
+      const double c = 1.0 - B.scale, ii0 = lane == 0 ? 1.0 : 0.0;
+      double dot = 0.0;
+      for (int j = 0; j < k; ++j) {
+        const double iij = lane == j ? 1.0 : 0.0;
+        const double v0 = iij + c * (ii0 - iij);
+        V[32 * j + lane] = v0;
+        dot = dot + v0 * lane_value(bx, j);
+      }
+      for (int j = 0; j < k; ++j) V[32 * j + lane] = (V[32 * j + lane] + v[0]) - dot;
+    }
+    bool hit = false;
+    for (uint32_t r = 1; r <= (uint32_t)MMB_SLICE_MAX_SHRINK; ++r) {
+      const double xb = ssx_draw(rs, r, k, g);
+      double x[R];
+      {
+        double acc = 0.0;
+        for (int j = 0; j < k; ++j) acc = acc + V[32 * j + lane] * lane_value(xb, j);
+        x[0] = acc;
+      }
+      bool rej = grp_any(lane < k && (x[0] < 0.0 || x[0] > 1.0));
+      if (!rej) rej = M::ssx_logf(A, B, s, g, x) < p0;
+      if (!rej) {
+        v[0] = x[0];
+        hit = true;
+        break;
+      }
+      const unsigned long long bal = __ballot(lane < k && xb < bx);
+      const uint32_t shr = (uint32_t)((threadIdx.x & 32) != 0 ? (bal >> 32) : bal);
+      double bc = xb;
+      for (int i = 0; i < k; ++i) {
+        if (((shr >> i) & 1u) == 0u) continue;
+        const double t = lane_value(bc, i), om = 1.0 - t;
+        const double vi = V[32 * i + lane];
+        for (int j = 0; j < k; ++j) {
+          if (j == i) continue;
+          const double vj = V[32 * j + lane];
+          V[32 * j + lane] = vj + t * (vi - vj);
+        }
+        bc = lane == i ? (bc - t) / om : bc / om;
+        bx = lane == i ? (bx - t) / om : bx / om;
+      }
+    }
+    if (!hit) slice_overflow(A, g);
+    M::relist(B, s, g, v);
   }
 
   // ---------------------------------------------------------------- pivoted Cholesky

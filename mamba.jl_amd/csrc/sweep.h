@@ -153,7 +153,14 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
           if constexpr ((KINDS >> MMB_SAMPLER_RWM) & 1u) S::rwm(A, B, c, chain, it, b, rn, ru, s, l, g, pk);
           break;
         case MMB_SAMPLER_DGS:
-          if constexpr ((KINDS >> MMB_SAMPLER_DGS) & 1u) S::dgs(A, B, ru, s, g);
+          if constexpr ((KINDS >> MMB_SAMPLER_DGS) & 1u)
+            S::template dgs<((KINDS >> MMB_SAMPLER_SLICESIMPLEX) & 1u) != 0u>(A, B, ru, s, g);
+          break;
+        case MMB_SAMPLER_SLICESIMPLEX:
+          if constexpr ((KINDS >> MMB_SAMPLER_SLICESIMPLEX) & 1u) {
+            const mmb_rng rs = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_SIMPLEX);
+            S::slice_simplex(A, B, ru, rs, s, g, M::ssx_rows(A, lds));
+          }
           break;
         case MMB_SAMPLER_GIBBS: if constexpr ((KINDS >> MMB_SAMPLER_GIBBS) & 1u) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
@@ -222,4 +229,6 @@ constexpr unsigned K_RWM = 1u << MMB_SAMPLER_RWM;
 // DGS likewise (node-IR models only): one more instantiation, which also holds RWM, so that a scheme
 // may mix DGS blocks with every other kind
 constexpr unsigned K_DGS = 1u << MMB_SAMPLER_DGS;
+// SliceSimplex likewise: the instantiation that schemes with such a block take holds every other kind
+constexpr unsigned K_SIMPLEX = 1u << MMB_SAMPLER_SLICESIMPLEX;
 

@@ -34,6 +34,13 @@ per node, in order (the reference loops over its keys, dgs.jl:61-80); a DGS node
 than 32 elements.  `x[T]` with T a sampled discrete node gathers by the state (x a sampled node or
 a data vector; T's support within 1..len(x), T as long as the expression).
 
+Probability vectors (src/samplers/slicesimplex.jl): `Dirichlet(alpha)` (alpha a constant list or a data
+vector, every alpha_i > 0) is one distribution over the 2..32 elements of a Stochastic(1, ...) node; a
+sampled one is updated by a `SliceSimplex` block only, and its initial values are probability vectors.
+SliceSimplex(["a", "b"]) becomes one device block per node, in order.  `Categorical(P)` with P such a
+sampled node reads its probabilities from the chain state (K = len(P)), so mixture weights are
+learnt (doc/examples/eyes.jl).  Arrays of Dirichlets (doc/examples/asthma.jl) are not lowered.
+
 User Gibbs blocks (ABI 10): `Sampler(params, f)` (src/samplers/sampler.jl:20-24) whose closure
 returns `rand(Normal(mu, sigma))`, `rand(InverseGamma(shape, scale))` or `rand(Gamma(shape,
 scale))` for one scalar node -- the conjugate full conditionals of doc/tutorial/line.jl:38-45
@@ -189,16 +196,35 @@ def Bernoulli(p): return Dist(abi.MMB_IR_BERNOULLI, p)
 
 
 def Categorical(p):
-    """Categorical(p): support 1..K; p a list of K constants or a data vector (an input), the same
-    for every element of the node."""
+    """Categorical(p): support 1..K; p a list of K constants, a data vector (an input) or a sampled
+    Dirichlet node (its K elements, read from the chain state), the same for every element of the node."""
     d = Dist(abi.MMB_IR_CATEGORICAL)
     if isinstance(p, Ref):
         d.p = p
     elif isinstance(p, Expr):
-        raise ArgumentError("Categorical(p): p is a constant list or a data vector")
+        raise ArgumentError("Categorical(p): p is a constant list, a data vector or a sampled Dirichlet node")
     else:
         d.p = np.atleast_1d(np.asarray(p, dtype=np.float64)).ravel()
     return d
+
+
+def Dirichlet(alpha):
+    """Dirichlet(alpha): alpha a list of constants or a data vector (an input), every alpha_i > 0; the
+    node's 2..32 elements are one probability vector."""
+    d = Dist(abi.MMB_IR_DIRICHLET)
+    if isinstance(alpha, Ref):
+        d.alpha = alpha
+    elif isinstance(alpha, Expr):
+        raise ArgumentError("Dirichlet(alpha): alpha is a constant list or a data vector")
+    else:
+        d.alpha = np.atleast_1d(np.asarray(alpha, dtype=np.float64)).ravel()
+        _check_alpha(d.alpha)
+    return d
+
+
+def _check_alpha(a):
+    if a.size < 1 or not np.all(np.isfinite(a)) or np.any(a <= 0.0):
+        raise ArgumentError("Dirichlet(alpha): every alpha must be positive")
 
 
 def DiscreteUniform(a, b):
@@ -246,6 +272,13 @@ _DISCRETE = {abi.MMB_IR_BINOMIAL, abi.MMB_IR_POISSON, abi.MMB_IR_BERNOULLI, abi.
 # DGSUnivariateDistribution (dgs.jl:6-8) without the two hypergeometrics
 _DGS_FAMILIES = _DISCRETE - {abi.MMB_IR_POISSON}
 _POSITIVE = {abi.MMB_IR_INVGAMMA, abi.MMB_IR_GAMMA, abi.MMB_IR_EXPONENTIAL}
+
+
+def _isprobvec(v):
+    """The support of a Dirichlet node (csrc/ir_math.h mmb_ir_dirichlet_lp): every entry >= 0 and
+    |sum - 1| <= MMB_SIMPLEX_TOL; a NaN fails."""
+    v = np.asarray(v, dtype=np.float64)
+    return bool(np.all(v >= 0.0) and abs(float(v.sum()) - 1.0) <= abi.MMB_SIMPLEX_TOL)
 
 
 # ------------------------------------------------------------------ nodes
@@ -306,11 +339,15 @@ class Model(_BaseModel):
     def setsamplers(self, samplers):
         # DGS(["a", "b"]) updates its keys one after another (dgs.jl:61-80): one device block per node,
         # in order, so that a block's terms are the node and that node's targets (dgs.jl:109-126 mass)
+        # SliceSimplex(["a", "b"]) likewise (slicesimplex.jl:37-54)
         split = []
         for s in samplers:
             if s.kind == abi.MMB_SAMPLER_DGS and len(s.params) != 1:
                 from .samplers import DGS
                 split += [DGS(p) for p in s.params]
+            elif s.kind == abi.MMB_SAMPLER_SLICESIMPLEX and len(s.params) != 1:
+                from .samplers import SliceSimplex
+                split += [SliceSimplex(p, scale=s.scale) for p in s.params]
             else:
                 split.append(s)
         samplers = split
@@ -355,6 +392,11 @@ class Model(_BaseModel):
                 lo, hi = self.support[n]
                 if v.size != self.lens[n] or np.any(v != np.round(v)) or np.any(v < lo) or np.any(v > hi):
                     raise ArgumentError(f"initial value of discrete node {n} (chain {k + 1}) is outside its support")
+        for k in range(chains):  # sampled Dirichlet nodes start on the simplex (validatesimplex, sampler.jl:80-82)
+            for n in self.simplex:
+                v = self._initval(inits[k], n)
+                if v.size != self.lens[n] or not _isprobvec(v):
+                    raise ArgumentError(f"variate is not a probability vector (node {n}, chain {k + 1})")
         for k in range(1, chains):  # fixed (observed) nodes are data: equal in every chain
             for n in self.fixed:
                 if not np.array_equal(self._initval(inits[k], n), self.fixed_vals[n]):
@@ -387,11 +429,17 @@ class Model(_BaseModel):
                     if fam not in _DGS_FAMILIES:
                         raise ArgumentError(f"DGS: node {n} is not a Bernoulli, Binomial, Categorical or "
                                             "DiscreteUniform node")
+                elif s.kind == abi.MMB_SAMPLER_SLICESIMPLEX:
+                    if fam != abi.MMB_IR_DIRICHLET:
+                        raise ArgumentError(f"SliceSimplex: node {n} is not a Dirichlet node")
+                elif fam == abi.MMB_IR_DIRICHLET:
+                    raise ArgumentError(f"Dirichlet node {n} cannot be sampled by {s!r}: use SliceSimplex")
                 elif fam in _DISCRETE:
                     raise ArgumentError(f"discrete node {n} cannot be sampled by {s!r}: use DGS")
                 elif fam not in _SAMPLEABLE:
                     raise ArgumentError(f"node {n}: its distribution family cannot be sampled by these samplers")
         self.discrete = [n for n in self.params if n in by_dgs]
+        self.simplex = [n for n in self.params if self.traced[n].fam == abi.MMB_IR_DIRICHLET]
         # state layout: sampled nodes in declaration order
         off = 0
         self.nodes = {}
@@ -627,12 +675,32 @@ class _Lowering:
         p = self.m.traced[name].p
         if isinstance(p, Ref):
             if self.kind(p.name) != "data":
-                raise ArgumentError(f"Categorical p of {name} must be a constant list or a data vector")
+                raise ArgumentError(f"Categorical p of {name} must be a constant list, a data vector or a sampled "
+                                    "Dirichlet node")
             p = self.m.inputs[p.name]
         if p.size < 1 or not np.all(np.isfinite(p)) or np.any(p < 0.0) or \
                 abs(float(p.sum()) - 1.0) > math.sqrt(np.finfo(float).eps):
             raise ArgumentError(f"Categorical p of {name} is not a probability vector")
         return p
+
+    def cat_state(self, name):
+        """The sampled Dirichlet node that Categorical node `name` reads its probabilities from, or None
+        (a constant list or a data vector: cat_p)."""
+        p = self.m.traced[name].p
+        if not isinstance(p, Ref) or p.name not in self.m.defs or self.kind(p.name) != "param":
+            return None
+        if self.m.traced[p.name].fam != abi.MMB_IR_DIRICHLET:
+            raise ArgumentError(f"Categorical p of {name}: the sampled node {p.name} is not a Dirichlet node")
+        return p.name
+
+    def dirichlet_alpha(self, name):
+        a = self.m.traced[name].alpha
+        if isinstance(a, Ref):
+            if self.kind(a.name) != "data":
+                raise ArgumentError(f"Dirichlet alpha of {name} must be a constant list or a data vector")
+            a = self.m.inputs[a.name]
+            _check_alpha(a)
+        return a
 
     def binomial_n(self, name):
         dist, ln = self.m.traced[name], self.m.lens[name]
@@ -652,7 +720,8 @@ class _Lowering:
                 raise ArgumentError(f"Binomial n of {name} must be non-negative integers")
             return 0, int(nn.max())
         if dist.fam == abi.MMB_IR_CATEGORICAL:
-            return 1, int(self.cat_p(name).size)
+            P = self.cat_state(name)
+            return 1, int(self.m.lens[P] if P is not None else self.cat_p(name).size)
         return dist.lo, dist.hi
 
     def expr(self, e, n, refs):
@@ -712,9 +781,21 @@ class _Lowering:
         for k, p in enumerate(ps):
             blk.gibbs_expr[k] = self.expr(p, 1, refs)
 
+    def cat_table(self, n, N, refs):
+        """cterm of Categorical node n: its probability table in the pool, or the state slots of the
+        sampled Dirichlet node it reads (which makes n a target of that node)."""
+        P = self.cat_state(n)
+        if P is None:
+            N.cterm = self.put(("catp", n), self.cat_p(n))
+        else:
+            refs.add(P)
+            N.cterm = -2 - self.m.nodes[P].offset  # MMB_IR_CAT_STATE(off), include/mamba_hip.h
+            self.m.no_predict[n] = f"a Categorical that reads the sampled node {P}"
+
     def run(self):
         m = self.m
         m.support = {}
+        m.no_predict = {}
         ids = {n: i for i, n in enumerate(m.order)}
         nodes = (abi.IrNode * len(m.order))()
         parents = {}
@@ -776,7 +857,7 @@ class _Lowering:
                         math.lgamma(a + 1) - math.lgamma(k + 1) - math.lgamma(a - k + 1) if k <= a else 0.0
                         for a in nn for k in range(hi + 1)])
                 elif dist.fam == abi.MMB_IR_CATEGORICAL:
-                    N.cterm = self.put(("catp", n), self.cat_p(n))
+                    self.cat_table(n, N, refs)
             elif dist.fam in (abi.MMB_IR_CATEGORICAL, abi.MMB_IR_DISCRETEUNIFORM):
                 lo, hi = self.support_bounds(n)
                 N.lo, N.hi = float(lo), float(hi)
@@ -784,7 +865,22 @@ class _Lowering:
                 if np.any(x != np.round(x)) or x.min() < lo or x.max() > hi:
                     raise ArgumentError(f"{n}: observations must be integers in {lo}..{hi}")
                 if dist.fam == abi.MMB_IR_CATEGORICAL:
-                    N.cterm = self.put(("catp", n), self.cat_p(n))
+                    self.cat_table(n, N, refs)
+            elif dist.fam == abi.MMB_IR_DIRICHLET:
+                # one Dirichlet over the node's elements: alpha[len], then lmnB, in the pool
+                if d.dim != 1:
+                    raise ArgumentError(f"Dirichlet node {n}: one Dirichlet is a Stochastic(1, ...) vector node "
+                                        "(arrays of Dirichlets are not lowered)")
+                al = self.dirichlet_alpha(n)
+                if al.size != ln:
+                    raise ArgumentError(f"Dirichlet node {n}: alpha has {al.size} elements, the node {ln}")
+                if not 2 <= ln <= abi.MMB_SIMPLEX_MAX:
+                    raise ArgumentError(f"Dirichlet node {n}: 2..{abi.MMB_SIMPLEX_MAX} elements (it has {ln})")
+                lmnb = math.fsum(math.lgamma(a) for a in al) - math.lgamma(math.fsum(al))
+                N.cterm = self.put(("diralpha", n), list(al) + [lmnb])
+                m.no_predict[n] = "a Dirichlet node"
+                if n not in m.params and not _isprobvec(m.fixed_vals[n]):
+                    raise ArgumentError(f"{n}: the observed value is not a probability vector")
             elif dist.fam in _DISCRETE:
                 x = m.fixed_vals[n]
                 if np.any(x != np.round(x)) or x.min() < 0:
@@ -841,6 +937,8 @@ class _Lowering:
             names += [n] if (d.dim == 0 and N.len == 1) else [f"{n}[{i + 1}]" for i in range(N.len)]
         if self.depth > abi.MMB_IR_MAX_STACK:
             raise ArgumentError("node expression too deep")
+        if not self.code:  # a model whose families take no parameter expression (Dirichlet, Categorical):
+            self.code.append(0)  # the engine asks for a code table, one END word
         m.monitor_names = names
         m.topo = topo
         # the node table of the model statistics (Model.keys, modelstats.py): an output node is an
@@ -1063,3 +1161,45 @@ def blocker_inits():
     return [{"rc": b["rc"], "rt": b["rt"], "d": 0, "delta_new": 0, "s2": 1, "mu": np.zeros(22), "delta": np.zeros(22)},
             {"rc": b["rc"], "rt": b["rt"], "d": 2, "delta_new": 2, "s2": 10, "mu": np.full(22, 2.0),
              "delta": np.full(22, 2.0)}]
+
+
+EYES_Y = [529.0, 530.0, 532.0, 533.1, 533.4, 533.6, 533.7, 534.1, 534.8, 535.3,   # doc/examples/eyes.jl:4-13
+          535.4, 535.9, 536.1, 536.3, 536.4, 536.6, 537.0, 537.4, 537.5, 538.3,
+          538.5, 538.6, 539.4, 539.6, 540.4, 540.8, 542.0, 542.8, 543.0, 543.5,
+          543.8, 543.9, 545.3, 546.2, 548.8, 548.7, 548.9, 549.0, 549.4, 549.9,
+          550.6, 551.2, 551.4, 551.5, 551.6, 552.8, 552.9, 553.2]
+
+
+def eyes_model(monitor_all=False):
+    """doc/examples/eyes.jl:17-61 (two-component normal mixture with the weight P ~ Dirichlet(alpha)
+    sampled).  The reference's lambda = [lambda0; lambda0 + theta] indexed by T is written
+    lambda0 + theta * (T - 1) -- the same two values, bit for bit, for T in {1, 2} -- and monitored as the
+    Logical `lam` = lambda0 + theta * step, step = [0, 1] (`lambda` is a Python keyword).
+    `monitor_all` also monitors T, lambda0 and theta, which the example does not."""
+    mon = bool(monitor_all)
+    return Model(
+        y=Stochastic(1, lambda lambda0, theta, T, s2: Normal(lambda0 + theta * (T - 1), sqrt(s2)), False),
+        T=Stochastic(1, lambda P: Categorical(P), mon),
+        P=Stochastic(1, lambda alpha: Dirichlet(alpha)),
+        lam=Logical(1, lambda lambda0, theta, step: lambda0 + theta * step),
+        lambda0=Stochastic(lambda: Normal(0.0, 1000.0), mon),
+        theta=Stochastic(lambda: Uniform(0.0, 1000.0), mon),
+        s2=Stochastic(lambda: InverseGamma(0.001, 0.001)))
+
+
+def eyes_inputs():
+    return {"alpha": [1.0, 1.0], "step": [0.0, 1.0]}
+
+
+def eyes_inits(y=None):
+    """doc/examples/eyes.jl:65-70 (`y`: other observations than the example's 48)."""
+    y = EYES_Y if y is None else list(y)
+    return [{"y": y, "T": [1.0] * len(y), "P": [0.5, 0.5], "lambda0": 535, "theta": 5, "s2": 10},
+            {"y": y, "T": [1.0] * len(y), "P": [0.5, 0.5], "lambda0": 550, "theta": 1, "s2": 1}]
+
+
+def eyes_scheme():
+    """doc/examples/eyes.jl:74-77"""
+    from .samplers import DGS, Slice, SliceSimplex
+    return [DGS("T"), Slice(["lambda0", "theta"], [5.0, 1.0]), Slice("s2", 2.0, transform=True),
+            SliceSimplex("P", scale=0.75)]

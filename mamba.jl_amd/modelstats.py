@@ -150,6 +150,10 @@ def predict_keys(model, nodekeys=None):
     outputs = model.keys("output")
     if not all(k in outputs for k in nodekeys):
         raise ArgumentError("nodekeys are not all observed Stochastic nodess : " + ", ".join(outputs))
+    for k in nodekeys:  # node-IR models: variates the predict kernel does not draw
+        why = getattr(model, "no_predict", {}).get(k)
+        if why:
+            raise ArgumentError(f"predict: node {k} is {why}: its variates are not lowered")
     return nodekeys
 
 

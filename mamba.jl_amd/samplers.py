@@ -13,6 +13,8 @@ Argument meaning, defaults and validation errors follow the reference:
   RWM(params, scale, proposal=Normal)                          src/samplers/rwm.jl:49-63
   DGS(params)  -- discrete Gibbs sampling of discrete nodes      src/samplers/dgs.jl:56-80
                   (node-IR models; no tuning, nothing adapts)
+  SliceSimplex(params, scale=1.0)  -- slice sampling of Dirichlet nodes on the simplex
+                  (node-IR models; no tuning, nothing adapts)   src/samplers/slicesimplex.jl:24-58
   Gibbs(params)  -- a user `Sampler(params, f)` whose f is the node's conjugate full
                     conditional (doc/tutorial/line.jl:27-45); lowered per model.
 """
@@ -89,7 +91,8 @@ class Sampler:
         return self.tuning
 
     def __repr__(self):
-        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS"}
+        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS",
+                 10: "SliceSimplex"}
         return f"{names[self.kind]}({self.params})"
 
 
@@ -182,6 +185,21 @@ def DGS(params):
     after another (dgs.jl:61-80), so a node-IR model lowers DGS(["a", "b"]) into one device block
     per node, in order (ir.Model.setsamplers).  No tuning state."""
     return Sampler(params, abi.MMB_SAMPLER_DGS, abi.MMB_ADAPT_NONE, None)
+
+
+def SliceSimplex(params, scale=1.0):
+    """SliceSimplex(params; scale=1.0) -- slicesimplex.jl:24-58: each Dirichlet node of `params` is updated
+    by slice sampling on its simplex, the first simplex shrunk by `scale` in (0, 1] (validate,
+    slicesimplex.jl:24-27).  Node-IR models only; like DGS, a node-IR model lowers
+    SliceSimplex(["a", "b"]) into one device block per node, in order (slicesimplex.jl:37-54).  No tuning
+    state, nothing adapts."""
+    try:
+        sc = float(scale)
+    except (TypeError, ValueError):
+        raise ArgumentError("scale is not in (0, 1]") from None
+    if not 0.0 < sc <= 1.0:
+        raise ArgumentError("scale is not in (0, 1]")
+    return Sampler(params, abi.MMB_SAMPLER_SLICESIMPLEX, abi.MMB_ADAPT_NONE, None, scale=sc)
 
 
 def Gibbs(params):
