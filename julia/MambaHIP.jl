@@ -7,7 +7,7 @@
 # file is not executed here: it is the code a maintainer adds as src/hip/MambaHIP.jl and
 # `include`s from src/Mamba.jl.  Its tested mirror is the Python host package:
 #   lower        <-> mamba.jl_amd/model.py  Model.spec() / samplers.py
-#   pack_tune    <-> the canonical tune layout of engine.cpp mmb_get_tune / mmb_set_tune
+#   pack_tune    <-> the canonical tune layout of engine_tune.cpp mmb_get_tune / mmb_set_tune
 #   run_chains!  <-> mamba.jl_amd/mcmc.py  mcmc() / mcmc_restart()
 #   gelmandiag   <-> mamba.jl_amd/gelman.py gelmandiag_rccl() (mmb_comm_* / mmb_gr_allreduce)
 module MambaHIP
@@ -846,7 +846,7 @@ function set_engine_values!(m::Model, kind, v::AbstractVector{Float64})
   end
 end
 
-# ---- tune <-> canonical engine tune row (engine.cpp mmb_get_tune / mmb_set_tune) -------------
+# ---- tune <-> canonical engine tune row (engine_tune.cpp mmb_get_tune / mmb_set_tune) -------------
 tri(i) = div(i * (i + 1), 2)                        # 0-based packed-lower helpers (device.h)
 slot(i, k) = i >= k ? tri(i) + k : tri(k) + i
 

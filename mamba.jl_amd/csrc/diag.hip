@@ -30,6 +30,7 @@
 #include "mamba_hip.h"
 #include "mmb_math.h"
 #include "order_key.h"
+#include "launch.h"
 
 #define DG_THREADS 64
 #define DG_PAIRS 8                 // lag pairs per IMSE / IPSE sweep

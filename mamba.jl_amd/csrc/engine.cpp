@@ -3,199 +3,14 @@
 // mmb_run is mcmc_master!/mcmc_worker! (src/model/mcmc.jl:36-83) for every chain of
 // this engine's shard: it launches the fused sweep kernel over windows of iterations
 // on the engine's stream and copies the kept draws out in Mamba's Chains order.
-#include <hip/hip_runtime.h>
+#include "engine.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
 #include <type_traits>
-#include <vector>
 
-#include "device.h"
-#include "models.h"
-#include "nuts.h"
-#include "logistic.h"
-#include "ir.h"
-#include "ir_jit.h"
-#include "predict_math.h"
+thread_local std::string g_last_error;
 
-#include <rccl/rccl.h>
-
-hipError_t mmb_launch_sweep(int model, unsigned kinds, const SweepArgs& A, hipStream_t st);
-hipError_t mmb_launch_order_chains(const OrderArgs& a, hipStream_t st);
-hipError_t mmb_launch_pchol_probe(int n, int d, const double* S, double* L, int32_t* pos, int32_t* info,
-                                  hipStream_t st);
-hipError_t mmb_lg_launch_ctl(const LgArgs& A, int start, int parity, int nbound, int fold, hipStream_t st);
-hipError_t mmb_lg_launch_grad(const LgArgs& A, int parity, int nbound, int fold, hipStream_t st);
-hipError_t mmb_launch_gr_range(int pmon, int64_t n, int K, const double* draws, double* out,
-                               hipStream_t st);
-hipError_t mmb_launch_chain_summary(int P, int64_t n, int K, int64_t kg0, int64_t bs, const double* draws,
-                                    const double* shift, double* out, hipStream_t st);
-hipError_t mmb_launch_order_hist(int P, int j, int64_t n, int K, const double* draws, int nt,
-                                 const uint64_t* prefix, int pass, unsigned long long* counts, hipStream_t st);
-hipError_t mmb_launch_gr_stats(int pmon, int64_t n, int K, const double* draws, const int32_t* link,
-                               const double* shift, double* stats, hipStream_t st);
-int mmb_gr_pmax();
-hipError_t mmb_launch_chain_autocov(int P, int K, int64_t i0, int64_t i1, int nlags, const int64_t* lags,
-                                    const double* draws, double* out, hipStream_t st);
-hipError_t mmb_launch_chain_mcse(int P, int K, int64_t i0, int64_t i1, int etype, int64_t bs, const double* draws,
-                                 double* out, hipStream_t st);
-hipError_t mmb_launch_change_counts(int P, int K, int64_t n, const double* draws, unsigned long long* out,
-                                    hipStream_t st);
-hipError_t mmb_launch_chain_cvm(int P, int K, int64_t n, int nstarts, const int64_t* starts, const double* draws,
-                                double* out, hipStream_t st);
-hipError_t mmb_launch_chain_mcse_from(int P, int K, const int64_t* i0s, int64_t i1, int etype, int64_t bs,
-                                      const double* draws, double* out, hipStream_t st);
-hipError_t mmb_launch_chain_raftery(int P, int K, int64_t n, int64_t rlo, int interp, double h, const double* draws,
-                                    double* out, hipStream_t st);
-// hpd.hip
-uint64_t mmb_hpd_key(double x);
-double mmb_hpd_unkey(uint64_t key);
-int64_t mmb_hpd_tiles(int64_t n);
-hipError_t mmb_launch_hpd_collect(int P, int j, int64_t n, int K, const double* draws, double lo, double hi,
-                                  int64_t cap, uint64_t* below, uint64_t* above, unsigned long long* meta,
-                                  hipStream_t st);
-hipError_t mmb_launch_hpd_sort(uint64_t* keys, uint64_t* tmp, int64_t n, uint64_t varying, unsigned int* tilehist,
-                               unsigned long long* ghist, int* in_tmp, hipStream_t st);
-hipError_t mmb_launch_hpd_gap(const uint64_t* below, int64_t nb, const uint64_t* above, int64_t na, int64_t m,
-                              double lo, double hi, double* part_d, long long* part_i, double* res, hipStream_t st);
-
-// modelstats.hip
-hipError_t mmb_launch_modelstats(int model, const SweepArgs& A, int nvalues, int stack, int64_t n, int K, int pmon,
-                                 const double* draws, int nnodes, const int32_t* nodes, const int32_t* col,
-                                 const int32_t* slot, int ncols, double* lp, hipStream_t st);
-hipError_t mmb_launch_deviance(int64_t rows, int K, const double* lp, double shift, double* acc, hipStream_t st);
-
-// predict.hip
-int mmb_predict_tile(int nvalues, int stack, int P, int* S, int* RS);
-hipError_t mmb_launch_predict(int model, const SweepArgs& A, int nvalues, int stack, int64_t n, int K, int pmon,
-                              const double* draws, int nnodes, const int32_t* nodes, const int32_t* col0, int P,
-                              const int32_t* col, const int32_t* slot, int ncols, uint64_t seed, int64_t it0,
-                              int64_t thin, double* yhat, hipStream_t st);
-hipError_t mmb_launch_predict_moments(int64_t rows, int K, int P, const double* yhat, const double* shift, double* acc,
-                                      hipStream_t st);
-
-hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* nwg, int* wg_per_cu);
-
-static thread_local std::string g_last_error;
-
-// chain parts of a sweep window (mmb_run): the engine stream and three more, as many streams as a
-// process has hardware queues by default (streams that share a queue serialise)
-constexpr int MMB_SWEEP_PARTS_MAX = 4;
-
-struct BlockHost {
-  mmb_block_spec spec;
-  std::vector<double> tuning;
-  int d = 0, T = 0, tune_len = 0;
-  std::vector<double> sigl;  // AMM chol(Sigma) lower row-major
-  bool sigl_diag = false;
-  // device
-  double *sigma = nullptr, *accept = nullptr, *Mv = nullptr, *Mvv = nullptr, *Ls = nullptr;
-  // AMM second moment buffers (32-lane kernels that carry proposals; DBlock::t_Mv_alt): chain k's
-  // current Mv / Mvv are in these when its m is odd.  Null: one buffer
-  double *Mv_alt = nullptr, *Mvv_alt = nullptr;
-  double *nuts = nullptr, *nfr = nullptr, *width = nullptr, *sigl_d = nullptr;
-  double* hmc = nullptr;  // HMC/MALA [K][2] epsilon, L
-  int32_t *m = nullptr, *flags = nullptr;
-  uint8_t* piv = nullptr;
-  double* xnext = nullptr;   // AMM carried next proposal [K][DP] (samplers.h amm)
-  int64_t* xtag = nullptr;   // AMM [K] tag of the carried proposal
-  uint64_t* astat = nullptr; // AMM [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats);
-                             // RWM: the same rows, [0] updates, [1] accepts (mmb_rwm_stats)
-  int32_t* sep_d = nullptr;  // node-IR AMWG: coordinate -> element-term table (ir_sep_table), engine lifetime
-  double sep_eps = 0.0;
-};
-
-struct mmb_engine {
-  mmb_model_spec spec{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int model = 0;
-  int P = 0, pmon = 0, VS = 0, DP = 0, TP = 0;
-  std::vector<BlockHost> blocks;
-  unsigned kinds = 0;  // bitmask of sampler kinds in the scheme
-  // data
-  std::vector<double> x, y, X;
-  bool have_data = false;
-  double* d_data = nullptr;
-  // chains
-  int64_t K = 0, chain_offset = 0;
-  uint64_t seed = 0;
-  int64_t iter = 0;
-  double* d_vals = nullptr;
-  DBlock* d_blocks = nullptr;
-  // logistic (config 4): padded X/y and the NUTS machine state (logistic.h)
-  int lg_N = 0, lg_p = 0, lg_rps = 0;
-  bool lg_fd = false;  // forward-difference gradient (MMB_GRAD_FORWARD): p + 1 columns per request
-  double *lg_X = nullptr, *lg_y = nullptr;
-  double *lg_vec = nullptr, *lg_sc = nullptr, *lg_frames = nullptr, *lg_pos = nullptr;
-  double *lg_gpart = nullptr, *lg_lpart = nullptr;
-  int32_t *lg_iv = nullptr, *lg_count = nullptr, *lg_hcount = nullptr, *lg_s2c = nullptr;
-  int64_t* lg_itc = nullptr;
-  hipEvent_t lg_cev[2 * MMB_LG_SPLIT_MAX] = {};  // request-count readbacks in flight, 2 per part (run_logistic)
-  hipStream_t lg_streamx[MMB_LG_SPLIT_MAX - 1] = {};   // the streams of parts 1.. (part 0: the engine stream)
-  hipEvent_t lg_join[MMB_LG_SPLIT_MAX] = {};          // fork / join of the streams
-  std::vector<hipEvent_t> evpoolx[MMB_LG_SPLIT_MAX - 1];  // kernel timing events of parts 1..
-  int64_t lg_steps = 0;  // gradient steps of the last window
-  unsigned long long* lg_ngrad = nullptr;
-  // sweep parts (mmb_run): the streams of parts 1.. (part 0: the engine stream), created on first use
-  hipStream_t sw_streamx[MMB_SWEEP_PARTS_MAX - 1] = {};
-  hipEvent_t sw_join[MMB_SWEEP_PARTS_MAX] = {};           // [0] fork, [i] join of part i
-  std::vector<hipEvent_t> sw_evpoolx[MMB_SWEEP_PARTS_MAX - 1];  // kernel timing events of parts 1..
-  int sw_resident = 0;  // workgroups of the sweep kernel the device holds at once (0: not asked yet)
-  int32_t* d_cperm = nullptr;  // lane-group slot -> chain of the 32-lane sweep kernels (order_chains)
-  bool cperm_identity = true;
-  bool order_fresh = false;    // d_cperm holds a table computed after a window (a host write of the
-                               // tune state clears it)
-  int64_t order_iter = 0;      // the iteration whose flags d_cperm was computed from
-  unsigned long long* d_nstat = nullptr;  // NUTS {updates, depth-cap hits, depth sum}, Slice overflows
-                                          // since init_chains
-  unsigned long long slice_overflows = 0;  // d_nstat[3] as last reported by mmb_run
-  int64_t xepoch = 0;  // bumped by every host write of chain state: invalidates carried AMM proposals
-  // draws of the last window
-  double* d_draws = nullptr;
-  size_t draws_cap = 0;
-  int64_t n_kept = 0;
-  // hpd tails (mmb_hpd_*): keys of the draws below / above the thresholds, a sort buffer as large and
-  // the sort's tile histograms, all for hpd_cap keys; grown on demand, freed in mmb_destroy
-  uint64_t *hpd_below = nullptr, *hpd_above = nullptr, *hpd_tmp = nullptr;
-  unsigned int* hpd_tilehist = nullptr;
-  unsigned long long* hpd_words = nullptr;  // meta, ghist, gap partials and result (HPD_WORDS)
-  int64_t hpd_cap = 0;
-  int64_t hpd_n[2] = {0, 0};                // keys held: below, above
-  uint64_t hpd_varying[2] = {0, 0};         // bits in which each buffer's keys differ (sort passes to run)
-  bool hpd_have = false, hpd_sorted = false;
-  // node IR (MMB_MODEL_IR): host copies of the lowered model, device tables
-  std::vector<mmb_ir_node> ir_nodes;
-  std::vector<int32_t> ir_code, ir_mon;
-  std::vector<double> ir_const, ir_pool;
-  std::vector<mmb_ir_block> ir_blocks;
-  int ir_stack = 0;
-  mmb_ir_node* d_ir_nodes = nullptr;
-  int32_t *d_ir_code = nullptr, *d_ir_mon = nullptr;
-  double *d_ir_const = nullptr, *d_ir_pool = nullptr;
-  mmb_ir_block* d_ir_blocks = nullptr;
-  // node IR specialised kernel (ir_jit.cpp): null when the interpreter kernel runs
-  hipModule_t jit_mod = nullptr;
-  hipFunction_t jit_fn = nullptr;
-  bool ir_noprop = false;  // specialised AMM + Gibbs kernel: no candidate copy of the state (ir.h NOPROP)
-  int ir_stack_dbl = 0;    // specialised kernel's expression-stack LDS doubles
-  int ssx_kmax = 0;        // elements of the widest SliceSimplex block (0: none)
-  std::string jit_info;
-  // timing
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<hipEvent_t> evpool;  // 2 per launch when time_kernels
-  double kernel_ms = 0.0;
-  int64_t launches = 0, units = 0;
-  std::string err;
-};
-
-static int fail(mmb_engine* e, int code, const char* fmt, ...) {
+int fail(mmb_engine* e, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -206,20 +21,7 @@ static int fail(mmb_engine* e, int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIPCHK(e, call)                                                                  \
-  do {                                                                                   \
-    hipError_t _st = (call);                                                             \
-    if (_st != hipSuccess)                                                               \
-      return fail((e), MMB_E_HIP, "%s failed: %s", #call, hipGetErrorString(_st));       \
-  } while (0)
-
-// families a DGS block may sample (dgs.jl:6-8 DGSUnivariateDistribution, without the hypergeometrics)
-static bool ir_dgs_family(int fam) {
-  return fam == MMB_IR_BINOMIAL || fam == MMB_IR_BERNOULLI || fam == MMB_IR_CATEGORICAL ||
-         fam == MMB_IR_DISCRETEUNIFORM;
-}
-
-static int node_dim(const mmb_model_spec& s, const mmb_ir_model* ir, int node, bool* positive) {
+int node_dim(const mmb_model_spec& s, const mmb_ir_model* ir, int node, bool* positive) {
   bool pos = false;
   int d = -1;
   if (s.model == MMB_MODEL_IR) {
@@ -243,110 +45,6 @@ static int node_dim(const mmb_model_spec& s, const mmb_ir_model* ir, int node, b
   }
   if (positive) *positive = pos;
   return d;
-}
-
-static int tri(int i) { return i * (i + 1) / 2; }
-
-// ---- node IR: AMWG blocks whose logpdf! separates by coordinate (lane-parallel decisions) ----
-// amwg_sub! (amwg.jl:99-115) evaluates logpdf!(m, x, block) once per coordinate.  The block's
-// terms (simulation.jl:77-90) are sums over node elements (logpdf_sub, distributionstruct.jl:
-// 136-168); when every element's term reads at most one coordinate of the block -- through the
-// node's own value or a parameter expression's VAL / VALI / VALG slot -- coordinate j's two
-// evaluations differ exactly in the terms of the elements that read j, whatever the accept
-// history of the other coordinates, so every coordinate's difference can be formed at once (ir.h
-// amwg_dm, samplers.h amwg_lanes).  The table lists, per coordinate, the (term, element) pairs
-// that read it, then the pairs that read none; an MvNormal term's sigma must read none.  The
-// gather indices are data, so this is built per engine at upload, not in the JIT source.
-// (VALV / DATAV index with a state value: the index node's slot, and for VALV the first slot of the
-// indexed node, which names its owner; *dyn tells a caller that needs the exact slots)
-static void ir_expr_slots(const std::vector<int32_t>& code, const std::vector<double>& pool, int pc, int i,
-                          std::vector<int>& slots, bool* dyn = nullptr) {
-  for (;; ++pc) {
-    const int w = code[pc];
-    const int op = (int)((uint32_t)w >> 24), arg = w & 0xffffff;
-    if (op == MMB_IR_OP_END) return;
-    if (op == MMB_IR_OP_VAL) slots.push_back(arg);
-    else if (op == MMB_IR_OP_VALI) slots.push_back(arg + i);
-    else if (op == MMB_IR_OP_VALG) slots.push_back(arg + (int)pool[code[++pc] + i]);
-    else if (op == MMB_IR_OP_VALV || op == MMB_IR_OP_DATAV) {
-      if (op == MMB_IR_OP_VALV) slots.push_back(arg);
-      slots.push_back(code[++pc] + i);
-      if (dyn) *dyn = true;
-    }
-  }
-}
-static bool ir_sep_table(const std::vector<mmb_ir_node>& nodes, const std::vector<int32_t>& code,
-                         const std::vector<double>& pool, const mmb_ir_block& IB, const mmb_block_spec& s,
-                         int nvalues, std::vector<int32_t>& tab, double* epsf) {
-  std::vector<int> coord((size_t)nvalues, -1);
-  int d = 0;
-  for (int a = 0; a < s.nnodes; ++a) {
-    const mmb_ir_node& N = nodes[s.nodes[a]];
-    for (int q = 0; q < N.len; ++q) coord[N.off + q] = d + q;
-    d += N.len;
-  }
-  if (d < 2 || d > 32) return false;
-  std::vector<std::vector<int32_t>> lists((size_t)d + 1);
-  int nmax = 1;
-  size_t total = 0;
-  std::vector<int> sl;
-  for (int t = 0; t < IB.nterms; ++t) {
-    const mmb_ir_node& N = nodes[IB.term[t]];
-    const bool iso = N.family == MMB_IR_ISONORMAL;
-    if (iso) {  // sigma (at element 0) must not read the block
-      sl.clear();
-      bool dyn = false;
-      ir_expr_slots(code, pool, N.expr[1], 0, sl, &dyn);
-      if (dyn) return false;
-      for (int q : sl)
-        if (coord[q] >= 0) return false;
-    }
-    nmax = std::max(nmax, (N.len + 31) / 32);
-    for (int i = 0; i < N.len; ++i) {
-      sl.clear();
-      if (!N.fixed) sl.push_back(N.off + i);
-      bool dyn = false;
-      for (int k = 0; k < (iso ? 1 : 2); ++k)
-        if (N.expr[k] >= 0) ir_expr_slots(code, pool, N.expr[k], i, sl, &dyn);
-      if (dyn) return false;  // a state-valued index: which coordinate the element reads is not fixed
-      int c = -1;
-      for (int q : sl) {
-        const int cq = coord[q];
-        if (cq < 0) continue;
-        if (c >= 0 && c != cq) return false;  // two coordinates: not separable
-        c = cq;
-      }
-      lists[c >= 0 ? c : d].push_back((int32_t)((t << 24) | i));
-      if (++total > (1u << 16)) return false;
-    }
-  }
-  tab.assign((size_t)d + 2, 0);
-  for (int j = 0; j <= d; ++j) {
-    tab[(size_t)j + 1] = tab[j] + (int32_t)lists[j].size();
-  }
-  for (int j = 0; j <= d; ++j) tab.insert(tab.end(), lists[j].begin(), lists[j].end());
-  // rounding band: each logf is a lane partial of <= nmax element terms, a 5-level butterfly, an
-  // MvNormal term's affine map and the sum over the terms, so it is within (nmax + nterms + 8) u
-  // of the exact sum of its element terms' magnitudes; 8x that, rounded up to a power of two
-  const int n = 8 * (nmax + IB.nterms + 8);
-  int e2 = 0;
-  while ((1 << e2) < n) ++e2;
-  *epsf = std::ldexp(1.0, e2 - 53);
-  return true;
-}
-
-static int tune_len_of(int kind, int d) {
-  switch (kind) {
-    case MMB_SAMPLER_AMWG: return 2 + 2 * d;
-    case MMB_SAMPLER_AMM: return 4 + 2 * d + 2 * tri(d);
-    case MMB_SAMPLER_NUTS: return 9;
-    case MMB_SAMPLER_HMC: return 2;   // [epsilon, L]     (HMCTune, hmc.jl:5-10)
-    case MMB_SAMPLER_MALA: return 1;  // [epsilon]        (MALATune, mala.jl:5-9)
-    case MMB_SAMPLER_RWM: return d;   // scale[d]         (RWMTune, rwm.jl:5-9)
-    case MMB_SAMPLER_DGS: return 0;   // no tuning state  (DGSTune holds only the mass function, dgs.jl:12-26)
-    case MMB_SAMPLER_SLICESIMPLEX: return 0;  // none either (SliceSimplexTune: logf and the constant scale)
-    default: return 0;
-  }
 }
 
 static int chol_lower(int d, const double* A, double* L) {  // A column-major
@@ -375,62 +73,7 @@ const char* mmb_last_error(const mmb_engine* e) {
   return g_last_error.c_str();
 }
 
-// Device form of the node IR's expressions: a leaf immediately followed by a binary op
-// (postfix "... x leaf op") becomes one fused word MMB_IR_FUSED + 4 (leaf - 1) + (op - ADD)
-// with the leaf's argument (VALG, VALV and DATAV keep their second word; the leaves end at 8, so
-// the fused opcodes end at 64 + 4 * 7 + 3 = 95, within the opcode byte): acc = acc op leaf instead of
-// spill, load, reload -- the same operands in the same order, so results are bit-identical
-// to the oracle, which interprets the unfused code.  Each distinct expression start is
-// rewritten once (validated code: every expression ends in END); node offsets are remapped.
-static void ir_fuse(const std::vector<int32_t>& code, std::vector<mmb_ir_node>& nodes,
-                    std::vector<mmb_ir_block>& blocks, std::vector<int32_t>& out) {
-  std::map<int32_t, int32_t> start;
-  auto op_of = [&](size_t pc) { return (int)((uint32_t)code[pc] >> 24); };
-  // every expression start: node parameters, then the Gibbs blocks' reductions and parameters
-  std::vector<int32_t*> exprs;
-  for (mmb_ir_node& N : nodes)
-    for (int k = 0; k < 3; ++k) exprs.push_back(&N.expr[k]);
-  for (mmb_ir_block& B : blocks) {
-    if (B.gibbs_family == 0) continue;
-    for (int r = 0; r < B.nred; ++r) exprs.push_back(&B.red_expr[r]);
-    for (int k = 0; k < 2; ++k) exprs.push_back(&B.gibbs_expr[k]);
-  }
-  for (int32_t* ex : exprs) {
-    {
-      const int32_t s0 = *ex;
-      if (s0 < 0) continue;
-      auto it = start.find(s0);
-      if (it == start.end()) {
-        const int32_t ns = (int32_t)out.size();
-        start[s0] = ns;
-        for (size_t pc = (size_t)s0;; ++pc) {
-          const int op = op_of(pc);
-          out.push_back(code[pc]);
-          if (op == MMB_IR_OP_END) break;
-          if (op >= 1 && op < 16) {
-            const bool two = op == MMB_IR_OP_VALG || op == MMB_IR_OP_VALV || op == MMB_IR_OP_DATAV;
-            const size_t nx = pc + (two ? 2 : 1);
-            const int bo = op_of(nx);
-            if (bo >= MMB_IR_OP_ADD && bo <= MMB_IR_OP_DIV) {
-              out.back() = (int32_t)(((uint32_t)(MMB_IR_FUSED + 4 * (op - 1) + (bo - MMB_IR_OP_ADD)) << 24) |
-                                     ((uint32_t)code[pc] & 0xffffffu));
-              if (two) out.push_back(code[pc + 1]);
-              pc = nx;  // the binary op is folded in
-              continue;
-            }
-            if (two) out.push_back(code[++pc]);
-          }
-        }
-        it = start.find(s0);
-      }
-      *ex = it->second;
-    }
-  }
-}
-
-static int ir_state_len(const mmb_model_spec* spec, const mmb_ir_model* ir);
-
-static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, mmb_engine** out) {
+int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, mmb_engine** out) {
   if (!spec || !out) return fail(nullptr, MMB_E_ARG, "null argument");
   *out = nullptr;
   if (spec->nblocks < 1 || spec->nblocks > MMB_MAX_BLOCKS)
@@ -664,7 +307,7 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
         }
     h.tune_len = tune_len_of(s.sampler, d);
     e->kinds |= 1u << s.sampler;
-    e->blocks.push_back(h);
+    e->blocks.push_back(std::move(h));
   }
   hipError_t st = hipSetDevice(device);
   if (st != hipSuccess) {
@@ -679,11 +322,11 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
   }
   if (e->model == MMB_MODEL_IR) {  // device copies of the IR tables (read-only for every launch)
     bool ok = true;
-    auto up = [&](auto** dst, const auto& v) {
+    auto up = [&](auto& dst, const auto& v) {
       using T = typename std::remove_reference<decltype(v)>::type::value_type;
       if (!ok) return;
-      ok = hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(T)) == hipSuccess &&
-           (v.empty() || hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
+      ok = dst.alloc(v.size()) == hipSuccess &&
+           (v.empty() || hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
     };
     {  // device code: every expression with its leaf+binop pairs fused (ir_fuse), padded
        // with END words (the interpreter fetches one word ahead, ir.h ev)
@@ -692,13 +335,13 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
       std::vector<int32_t> code;
       ir_fuse(e->ir_code, nodes, blocks, code);
       code.resize(code.size() + 2, 0);
-      up(&e->d_ir_nodes, nodes);
-      up(&e->d_ir_code, code);
-      up(&e->d_ir_blocks, blocks);
+      up(e->d_ir_nodes, nodes);
+      up(e->d_ir_code, code);
+      up(e->d_ir_blocks, blocks);
     }
-    up(&e->d_ir_const, e->ir_const);
-    up(&e->d_ir_pool, e->ir_pool);
-    up(&e->d_ir_mon, e->ir_mon);
+    up(e->d_ir_const, e->ir_const);
+    up(e->d_ir_pool, e->ir_pool);
+    up(e->d_ir_mon, e->ir_mon);
     // AMWG blocks whose logpdf! separates by coordinate: lane-parallel decisions in the specialised
     // kernel (MMB_IR_SEP=0 keeps every block on amwg_sub!'s sequential loop)
     const char* se = std::getenv("MMB_IR_SEP");
@@ -708,7 +351,7 @@ static int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int d
       std::vector<int32_t> tab;
       if (h.spec.sampler == MMB_SAMPLER_AMWG &&
           ir_sep_table(e->ir_nodes, e->ir_code, e->ir_pool, e->ir_blocks[b], h.spec, e->P, tab, &h.sep_eps))
-        up(&h.sep_d, tab);
+        up(h.sep_d, tab);
     }
     if (!ok) {
       mmb_destroy(e);
@@ -725,436 +368,14 @@ int mmb_create(const mmb_model_spec* spec, int device, mmb_engine** out) {
   return create_impl(spec, nullptr, device, out);
 }
 
-// Host-side validation of a node IR: every code word, slot, pool range and gather index is
-// checked against the node lengths, so no kernel can address outside its LDS row or the pool.
-static int ir_check_expr(const mmb_ir_model* ir, int pc, int len, int* depth, int vlim = -1) {
-  // vlim: value slots the expression may read (default nvalues; a Gibbs block's parameter
-  // expressions also read its reduction slots nvalues .. nvalues + nred - 1)
-  if (vlim < 0) vlim = ir->nvalues;
-  int sp = 0, mx = 0;
-  for (int steps = 0; steps < ir->ncode + 1; ++steps, ++pc) {
-    if (pc < 0 || pc >= ir->ncode) return -1;
-    const int w = ir->code[pc];
-    const int op = (int)((uint32_t)w >> 24), arg = w & 0xffffff;
-    if (op == MMB_IR_OP_END) {
-      if (sp != 1) return -1;
-      *depth = std::max(*depth, mx);
-      return 0;
-    }
-    if (op < 16) {
-      switch (op) {
-        case MMB_IR_OP_CONST: if (arg >= ir->nconst) return -1; break;
-        case MMB_IR_OP_VAL: if (arg >= vlim) return -1; break;
-        case MMB_IR_OP_VALI: if ((int64_t)arg + len > vlim) return -1; break;
-        case MMB_IR_OP_VALG: {
-          if (++pc >= ir->ncode) return -1;
-          const int64_t w2 = ir->code[pc];
-          if (w2 < 0 || w2 + len > ir->npool) return -1;
-          for (int i = 0; i < len; ++i) {
-            const double q = ir->pool[w2 + i];
-            if (!(q >= 0.0) || q != (double)(int64_t)q || (int64_t)arg + (int64_t)q >= vlim) return -1;
-          }
-          break;
-        }
-        case MMB_IR_OP_DATA: if ((int64_t)arg + len > ir->npool) return -1; break;
-        case MMB_IR_OP_DATAS: if ((int64_t)arg >= ir->npool) return -1; break;
-        case MMB_IR_OP_VALV:
-        case MMB_IR_OP_DATAV: {
-          // x[T]: the second word is the first state slot of a sampled discrete node T of exactly
-          // `len` elements, whose support lo..hi (integers, >= 1) stays inside the indexed table
-          if (++pc >= ir->ncode) return -1;
-          const int64_t w2 = ir->code[pc];
-          const mmb_ir_node* T = nullptr;
-          for (int q = 0; q < ir->nnodes; ++q) {
-            const mmb_ir_node& Q = ir->nodes[q];
-            if (!Q.fixed && ir_dgs_family(Q.family) && Q.off == w2 && Q.len == len) T = &Q;
-          }
-          if (!T || !(T->lo >= 1.0) || !(T->hi >= T->lo) || !(T->hi < 16777216.0)) return -1;
-          const int64_t top = (int64_t)arg + (int64_t)T->hi - 1;
-          if (top >= (op == MMB_IR_OP_VALV ? (int64_t)ir->nvalues : ir->npool)) return -1;
-          break;
-        }
-        default: return -1;
-      }
-      ++sp;
-      mx = std::max(mx, sp);
-    } else if (op < 32) {
-      if (op > MMB_IR_OP_DIV || sp < 2) return -1;
-      --sp;
-    } else if (op > MMB_IR_OP_ABS || sp < 1) {
-      return -1;
-    }
-  }
-  return -1;
-}
-
-static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
-  if (spec->model != MMB_MODEL_IR) return fail(nullptr, MMB_E_ARG, "spec->model must be MMB_MODEL_IR");
-  if (ir->nvalues < 1 || ir->nvalues > MMB_IR_MAX_VALUES)
-    return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: 1 <= nvalues <= %d", MMB_IR_MAX_VALUES);
-  if (ir->nnodes < 1 || !ir->nodes || ir->ncode < 1 || !ir->code || ir->npool < 0 || (ir->npool > 0 && !ir->pool) ||
-      ir->nconst < 0 || (ir->nconst > 0 && !ir->consts) || ir->nmon < 0 || (ir->nmon > 0 && !ir->mon))
-    return fail(nullptr, MMB_E_ARG, "node IR: missing tables");
-  if (ir->npool >= (1 << 24) || ir->nconst >= (1 << 24))  // code-word operands are 24-bit
-    return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: pool and constant tables must hold < 2^24 entries");
-  if (ir->stack < 1 || ir->stack > MMB_IR_MAX_STACK)
-    return fail(nullptr, MMB_E_ARG, "node IR: stack depth must be 1..%d", MMB_IR_MAX_STACK);
-  int depth = 0;
-  for (int n = 0; n < ir->nnodes; ++n) {
-    const mmb_ir_node& N = ir->nodes[n];
-    if (N.family < MMB_IR_NORMAL || N.family > MMB_IR_DIRICHLET || N.len < 1)
-      return fail(nullptr, MMB_E_ARG, "node IR: node %d has a bad family or length", n);
-    if (N.family != MMB_IR_LOGICAL) {
-      const int64_t end = (int64_t)N.off + N.len;
-      if (N.off < 0 || end > (N.fixed ? ir->npool : (int64_t)ir->nvalues))
-        return fail(nullptr, MMB_E_ARG, "node IR: node %d values out of range", n);
-    }
-    if (N.family == MMB_IR_POISSON && !N.fixed)  // (infinite support: no DGS)
-      return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: Poisson node %d must be fixed (observed)", n);
-    const bool dgs = !N.fixed && ir_dgs_family(N.family);
-    if (dgs) {  // a sampled discrete node: in exactly the DGS blocks, one node each (create_impl), never another kind
-      bool in_dgs = false;
-      for (int b = 0; b < spec->nblocks; ++b)
-        for (int a = 0; a < spec->blocks[b].nnodes && a < MMB_MAX_NODES_PER_BLOCK; ++a)
-          if (spec->blocks[b].nodes[a] == n) {
-            if (spec->blocks[b].sampler != MMB_SAMPLER_DGS)
-              return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d can be sampled by a DGS block only", n);
-            in_dgs = true;
-          }
-      if (!in_dgs) return fail(nullptr, MMB_E_ARG, "node IR: sampled discrete node %d is in no DGS block", n);
-    }
-    // integer support lo..hi of at most MMB_DGS_MAX_SUPPORT values: Categorical and DiscreteUniform
-    // always (their density reads it), Bernoulli and Binomial when sampled
-    if (dgs || N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM) {
-      const bool ints = N.lo == std::floor(N.lo) && N.hi == std::floor(N.hi) && std::fabs(N.lo) < 16777216.0;
-      if (!ints || !(N.hi >= N.lo) || (dgs && N.hi - N.lo + 1.0 > (double)MMB_DGS_MAX_SUPPORT))
-        return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d needs an integer support of at most %d values", n,
-                    MMB_DGS_MAX_SUPPORT);
-      if (N.family == MMB_IR_CATEGORICAL && N.lo != 1.0)
-        return fail(nullptr, MMB_E_ARG, "node IR: Categorical node %d has support 1..K", n);
-      if ((N.family == MMB_IR_BINOMIAL || N.family == MMB_IR_BERNOULLI) &&
-          (N.lo != 0.0 || (N.family == MMB_IR_BERNOULLI && N.hi != 1.0)))
-        return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d has a bad support", n);
-    }
-    if (N.family == MMB_IR_DIRICHLET) {
-      // one Dirichlet per node, an element per lane; alpha[len] > 0 and lmnB in the pool.  A sampled one
-      // is in SliceSimplex blocks only (one node each: create_impl), and in at least one
-      if (N.len < 2 || N.len > MMB_SIMPLEX_MAX)
-        return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d needs 2..%d elements", n, MMB_SIMPLEX_MAX);
-      if (N.cterm < 0 || (int64_t)N.cterm + N.len + 1 > ir->npool)
-        return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d needs alpha[len] and lmnB in the pool", n);
-      for (int i = 0; i < N.len; ++i)
-        if (!(ir->pool[N.cterm + i] > 0.0 && std::isfinite(ir->pool[N.cterm + i])))
-          return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d: alpha[%d] must be positive", n, i);
-      if (!std::isfinite(ir->pool[N.cterm + N.len]))
-        return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d: lmnB is not finite", n);
-      if (!N.fixed) {
-        bool in_ssx = false;
-        for (int b = 0; b < spec->nblocks; ++b)
-          for (int a = 0; a < spec->blocks[b].nnodes && a < MMB_MAX_NODES_PER_BLOCK; ++a)
-            if (spec->blocks[b].nodes[a] == n) {
-              if (spec->blocks[b].sampler != MMB_SAMPLER_SLICESIMPLEX)
-                return fail(nullptr, MMB_E_ARG, "node IR: Dirichlet node %d can be sampled by a SliceSimplex block only", n);
-              in_ssx = true;
-            }
-        if (!in_ssx) return fail(nullptr, MMB_E_ARG, "node IR: sampled Dirichlet node %d is in no SliceSimplex block", n);
-      }
-    } else if (mmb_ir_cat_state(N.family, N.cterm) >= 0) {
-      // Categorical(P): the K = hi probabilities are the state slots of one sampled Dirichlet node of length K
-      const int po = mmb_ir_cat_state(N.family, N.cterm);
-      bool ok = false;
-      for (int q = 0; q < ir->nnodes; ++q) {
-        const mmb_ir_node& Q = ir->nodes[q];
-        if (!Q.fixed && Q.family == MMB_IR_DIRICHLET && Q.off == po && (double)Q.len == N.hi) ok = true;
-      }
-      if (!ok)
-        return fail(nullptr, MMB_E_ARG, "node IR: Categorical node %d: its probabilities must be the slots of one "
-                    "sampled Dirichlet node of length K", n);
-    } else {  // constant table: per element; sampled Binomial (element, value); Categorical K probabilities
-      int64_t nct = N.len;
-      if (N.family == MMB_IR_CATEGORICAL) nct = (int64_t)N.hi;
-      else if (N.family == MMB_IR_BINOMIAL && dgs) nct = (int64_t)N.len * ((int64_t)N.hi + 1);
-      if ((N.family == MMB_IR_CATEGORICAL || (N.family == MMB_IR_BINOMIAL && dgs)) && N.cterm < 0)
-        return fail(nullptr, MMB_E_ARG, "node IR: node %d needs its constant table", n);
-      if (N.cterm >= 0 && (int64_t)N.cterm + nct > ir->npool)
-        return fail(nullptr, MMB_E_ARG, "node IR: node %d constant term out of range", n);
-    }
-    if (N.family == MMB_IR_BINOMIAL && dgs) {
-      // n is data, one DATA / DATAS word, so that the support 0..n_i of every element is known here
-      const int pc = N.expr[0];
-      if (pc < 0 || pc + 1 >= ir->ncode || ir->code[pc + 1] != 0)
-        return fail(nullptr, MMB_E_ARG, "node IR: sampled Binomial node %d: n must be one data word", n);
-      const int op = (int)((uint32_t)ir->code[pc] >> 24), arg = ir->code[pc] & 0xffffff;
-      if (op != MMB_IR_OP_DATA && op != MMB_IR_OP_DATAS)
-        return fail(nullptr, MMB_E_ARG, "node IR: sampled Binomial node %d: n must be one data word", n);
-      for (int i = 0; i < N.len; ++i) {
-        const int64_t at = (int64_t)arg + (op == MMB_IR_OP_DATA ? i : 0);
-        if (at >= ir->npool) return fail(nullptr, MMB_E_ARG, "node IR: node %d parameter 0 has invalid code", n);
-        const double nn = ir->pool[at];
-        if (!(nn >= 0.0 && nn <= N.hi && nn == std::floor(nn)))
-          return fail(nullptr, MMB_E_ARG, "node IR: sampled Binomial node %d: n[%d] must be an integer in 0..%d", n, i,
-                      (int)N.hi);
-      }
-    }
-    const int nexpr = N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM ||
-                              N.family == MMB_IR_DIRICHLET ? 0
-                      : N.family == MMB_IR_LOGICAL || N.family == MMB_IR_EXPONENTIAL || N.family == MMB_IR_POISSON ||
-                              N.family == MMB_IR_BERNOULLI ? 1 : 2;
-    for (int k = 0; k < 3; ++k) {
-      if (k >= nexpr) {
-        if (N.expr[k] >= 0) return fail(nullptr, MMB_E_ARG, "node IR: node %d has extra parameters", n);
-        continue;
-      }
-      if (ir_check_expr(ir, N.expr[k], N.family == MMB_IR_ISONORMAL && k == 1 ? 1 : N.len, &depth))
-        return fail(nullptr, MMB_E_ARG, "node IR: node %d parameter %d has invalid code", n, k);
-    }
-  }
-  if (depth > ir->stack) return fail(nullptr, MMB_E_ARG, "node IR: stack depth %d exceeds %d", depth, ir->stack);
-  for (int q = 0; q < ir->nmon; ++q)
-    if (ir->mon[q] < 0 || ir->mon[q] >= ir->nnodes) return fail(nullptr, MMB_E_ARG, "node IR: bad monitored node");
-  if (spec->nblocks < 1 || spec->nblocks > MMB_MAX_BLOCKS)
-    return fail(nullptr, MMB_E_ARG, "nblocks must be in 1..%d", MMB_MAX_BLOCKS);
-  for (int b = 0; b < spec->nblocks; ++b) {
-    const mmb_ir_block& B = ir->blocks[b];
-    const bool gibbs = spec->blocks[b].sampler == MMB_SAMPLER_GIBBS;
-    if (B.nterms < (gibbs ? 0 : 1) || B.nterms > MMB_IR_MAX_TERMS)
-      return fail(nullptr, MMB_E_ARG, "node IR: block %d terms", b);
-    for (int t = 0; t < B.nterms; ++t)
-      if (B.term[t] < 0 || B.term[t] >= ir->nnodes || ir->nodes[B.term[t]].family == MMB_IR_LOGICAL)
-        return fail(nullptr, MMB_E_ARG, "node IR: block %d term %d invalid", b, t);
-    if (spec->blocks[b].sampler == MMB_SAMPLER_DGS && B.term[0] != spec->blocks[b].nodes[0])
-      return fail(nullptr, MMB_E_ARG, "node IR: DGS block %d: its terms are its node, then the node's targets", b);
-    if (spec->blocks[b].sampler == MMB_SAMPLER_SLICESIMPLEX && B.term[0] != spec->blocks[b].nodes[0])
-      return fail(nullptr, MMB_E_ARG, "node IR: SliceSimplex block %d: its terms are its node, then the node's targets", b);
-    // a Dirichlet node has no sampled parent and a state-read Categorical only its P: they are terms of
-    // SliceSimplex and DGS blocks alone, and only those blocks' log densities know them (ir.h elem_lp<SX>)
-    if (spec->blocks[b].sampler != MMB_SAMPLER_SLICESIMPLEX && spec->blocks[b].sampler != MMB_SAMPLER_DGS)
-      for (int t = 0; t < B.nterms; ++t) {
-        const mmb_ir_node& Q = ir->nodes[B.term[t]];
-        if (Q.family == MMB_IR_DIRICHLET || mmb_ir_cat_state(Q.family, Q.cterm) >= 0)
-          return fail(nullptr, MMB_E_ARG, "node IR: block %d term %d: a Dirichlet node or a Categorical that reads one "
-                      "is a term of SliceSimplex and DGS blocks only", b, t);
-      }
-    if (!gibbs) {
-      if (B.gibbs_family != 0) return fail(nullptr, MMB_E_ARG, "node IR: block %d is not a Gibbs block", b);
-      continue;
-    }
-    // a Gibbs closure block (ABI 10): conjugate family, reductions over <= 2^24 elements, scalar
-    // parameter expressions that may read the block's reduction slots
-    if (B.gibbs_family != MMB_IR_NORMAL && B.gibbs_family != MMB_IR_INVGAMMA && B.gibbs_family != MMB_IR_GAMMA)
-      return fail(nullptr, MMB_E_UNSUPPORTED,
-                  "node IR: Gibbs block %d must draw rand(Normal | InverseGamma | Gamma) (a lowered closure)", b);
-    if (B.nred < 0 || B.nred > MMB_IR_MAX_RED) return fail(nullptr, MMB_E_ARG, "node IR: block %d reductions", b);
-    for (int r = 0; r < B.nred; ++r)
-      if (B.red_len[r] < 1 || B.red_len[r] >= (1 << 24) || ir_check_expr(ir, B.red_expr[r], B.red_len[r], &depth))
-        return fail(nullptr, MMB_E_ARG, "node IR: block %d reduction %d has invalid code", b, r);
-    for (int k = 0; k < 2; ++k)
-      if (ir_check_expr(ir, B.gibbs_expr[k], 1, &depth, ir->nvalues + B.nred))
-        return fail(nullptr, MMB_E_ARG, "node IR: block %d Gibbs parameter %d has invalid code", b, k);
-    if (depth > ir->stack) return fail(nullptr, MMB_E_ARG, "node IR: stack depth %d exceeds %d", depth, ir->stack);
-  }
-  return 0;
-}
-
-// value slots of the state row: nvalues, then the widest Gibbs block's reduction results
-static int ir_state_len(const mmb_model_spec* spec, const mmb_ir_model* ir) {
-  int nred = 0;
-  for (int b = 0; b < spec->nblocks; ++b)
-    if (spec->blocks[b].sampler == MMB_SAMPLER_GIBBS) nred = std::max(nred, (int)ir->blocks[b].nred);
-  return ir->nvalues + nred;
-}
-
-// Sampler kinds of the scheme and its widest AMM block (the specialised kernel's parameters)
-static void ir_jit_params(const mmb_model_spec* spec, const mmb_ir_model* ir, unsigned* kinds, int* dmax) {
-  *kinds = 0;
-  *dmax = 0;
-  for (int b = 0; b < spec->nblocks; ++b) {
-    const mmb_block_spec& s = spec->blocks[b];
-    *kinds |= 1u << s.sampler;
-    int d = 0;
-    for (int a = 0; a < s.nnodes; ++a) d += std::max(0, node_dim(*spec, ir, s.nodes[a], nullptr));
-    if (s.sampler == MMB_SAMPLER_AMM) *dmax = std::max(*dmax, d);
-  }
-  if (*dmax == 0) *dmax = Mdl<MMB_MODEL_IR>::DMAX;  // no AMM block: the factorization is not compiled
-}
-
-// The generator (ir_jit.cpp) writes no code for DGS blocks, the discrete families they sample or the
-// state-indexed leaves VALV / DATAV, which only such schemes hold: it declines those schemes whole
-static const char* const kJitNoDgs = "the specialised kernel declines schemes with DGS blocks: sampled discrete "
-                                     "nodes and state-indexed gathers are not generated";
-// Nor for SliceSimplex blocks, the Dirichlet density or a Categorical that reads its probabilities
-// from the state
-static const char* const kJitNoSimplex = "the specialised kernel declines schemes with SliceSimplex blocks and "
-                                         "models with a Dirichlet node or a Categorical that reads a sampled P: "
-                                         "they are not generated";
-// why the generator declines the scheme (null: it does not)
-static const char* ir_jit_declined(unsigned kinds, const mmb_ir_model* ir) {
-  if (kinds & (1u << MMB_SAMPLER_SLICESIMPLEX)) return kJitNoSimplex;
-  for (int n = 0; n < ir->nnodes; ++n)
-    if (ir->nodes[n].family == MMB_IR_DIRICHLET || mmb_ir_cat_state(ir->nodes[n].family, ir->nodes[n].cterm) >= 0)
-      return kJitNoSimplex;
-  if (kinds & (1u << MMB_SAMPLER_DGS)) return kJitNoDgs;
-  return nullptr;
-}
-
-// The specialised kernel of a node-IR engine (ir_jit.cpp); on any failure the interpreter
-// kernel runs (jit_info says why).  MMB_IR_JIT=0 selects the interpreter.
-static void ir_jit_setup(mmb_engine* e, const mmb_model_spec* spec, const mmb_ir_model* ir) {
-  const char* env = std::getenv("MMB_IR_JIT");
-  if (env && std::string(env) == "0") {
-    e->jit_info = "interpreter (MMB_IR_JIT=0)";
-    return;
-  }
-  unsigned kinds = 0;
-  int dmax = 0;
-  ir_jit_params(spec, ir, &kinds, &dmax);
-  if (const char* why = ir_jit_declined(kinds, ir)) {
-    e->jit_info = std::string("interpreter (") + why + ")";
-    return;
-  }
-  std::vector<char> code;
-  std::string info;
-  if (mmb_ir_jit_obtain(mmb_ir_jit_source(*spec, *ir, kinds, dmax), &code, &info)) {
-    e->jit_info = "interpreter (specialisation failed: " + info + ")";
-    return;
-  }
-  hipModule_t mod = nullptr;
-  hipFunction_t fn = nullptr;
-  hipError_t st = hipSetDevice(e->device);
-  if (st == hipSuccess) st = hipModuleLoadData(&mod, code.data());
-  if (st == hipSuccess) st = hipModuleGetFunction(&fn, mod, "mmb_ir_jit_kernel");
-  if (st != hipSuccess) {
-    if (mod) (void)hipModuleUnload(mod);
-    e->jit_info = std::string("interpreter (module load failed: ") + hipGetErrorString(st) + ")";
-    return;
-  }
-  e->jit_mod = mod;
-  e->jit_fn = fn;
-  // the specialised kernel's layout (ir_jit.h): AMM triangle sized to the widest AMM block, no
-  // candidate state copy for AMM + Gibbs schemes, no expression stack beyond AMWG's term weights
-  // (set before mmb_init_chains allocates the per-chain arrays)
-  e->TP = mmb_ir_jit_tp(dmax);
-  e->ir_noprop = mmb_ir_jit_noprop(kinds);
-  e->ir_stack_dbl = mmb_ir_jit_stack_dbl(kinds);
-  e->jit_info = "specialised kernel (" + info + ")";
-  int namwg = 0, nsep = 0;
-  for (const BlockHost& h : e->blocks)
-    if (h.spec.sampler == MMB_SAMPLER_AMWG) {
-      ++namwg;
-      nsep += h.sep_d != nullptr;
-    }
-  if (namwg) e->jit_info += "; lane-parallel AMWG blocks: " + std::to_string(nsep) + " of " + std::to_string(namwg);
-}
-
-int mmb_create_ir(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, mmb_engine** out) {
-  if (!spec || !ir || !out) return fail(nullptr, MMB_E_ARG, "null argument");
-  int rc = ir_validate(spec, ir);
-  if (rc) return rc;
-  rc = create_impl(spec, ir, device, out);
-  if (rc) return rc;
-  ir_jit_setup(*out, spec, ir);
-  if ((*out)->ssx_kmax > 0) {
-    // SliceSimplex schemes run the interpreter with the vertex rows appended to each chain's LDS
-    // (fill_args): four chains per 128-thread workgroup must fit the 64 KiB of a launch
-    const mmb_engine* e = *out;
-    const int G = Mdl<MMB_MODEL_IR>::G;
-    const int64_t per_chain = ((e->kinds & (1u << MMB_SAMPLER_AMM)) ? e->TP + 4 * Mdl<MMB_MODEL_IR>::DP + 2 : 0) +
-                              2 * (int64_t)e->VS + (int64_t)(e->ir_stack + 1) * G + (int64_t)e->ssx_kmax * G;
-    if (per_chain * (128 / G) * (int64_t)sizeof(double) > 65536) {
-      mmb_destroy(*out);
-      *out = nullptr;
-      return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: the scheme's LDS (%lld doubles per chain with the SliceSimplex "
-                  "vertex rows) exceeds a workgroup's 64 KiB", (long long)per_chain);
-    }
-  }
-  return 0;
-}
-
-int mmb_ir_jit_prebuild(const mmb_model_spec* spec, const mmb_ir_model* ir, char* info, int64_t n) {
-  if (!spec || !ir) return fail(nullptr, MMB_E_ARG, "null argument");
-  int rc = ir_validate(spec, ir);
-  if (rc) return rc;
-  unsigned kinds = 0;
-  int dmax = 0;
-  ir_jit_params(spec, ir, &kinds, &dmax);
-  if (const char* why = ir_jit_declined(kinds, ir)) {
-    if (info && n > 0) snprintf(info, (size_t)n, "%s", why);
-    return fail(nullptr, MMB_E_UNSUPPORTED, "%s", why);
-  }
-  std::vector<char> code;
-  std::string msg;
-  rc = mmb_ir_jit_obtain(mmb_ir_jit_source(*spec, *ir, kinds, dmax), &code, &msg);
-  if (info && n > 0) snprintf(info, (size_t)n, "%s", msg.c_str());
-  return rc ? fail(nullptr, MMB_E_UNSUPPORTED, "%s", msg.c_str()) : 0;
-}
-
-int mmb_ir_jit_source_text(const mmb_model_spec* spec, const mmb_ir_model* ir, char* buf, int64_t n) {
-  if (!spec || !ir) return fail(nullptr, MMB_E_ARG, "null argument");
-  int rc = ir_validate(spec, ir);
-  if (rc) return rc;
-  unsigned kinds = 0;
-  int dmax = 0;
-  ir_jit_params(spec, ir, &kinds, &dmax);
-  if (const char* why = ir_jit_declined(kinds, ir)) return fail(nullptr, MMB_E_UNSUPPORTED, "%s", why);
-  const std::string src = mmb_ir_jit_source(*spec, *ir, kinds, dmax);
-  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", src.c_str());
-  return (int)std::min<size_t>(src.size(), (size_t)INT32_MAX);
-}
-
-int mmb_ir_jit_info(const mmb_engine* e, char* buf, int64_t n) {
-  if (!e) return fail(nullptr, MMB_E_ARG, "null argument");
-  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", e->model == MMB_MODEL_IR ? e->jit_info.c_str() : "not a node-IR engine");
-  return e->jit_fn ? 1 : 0;
-}
-
+// drops the per-chain device state (the next mmb_init_chains, mmb_destroy)
 static void free_dev(mmb_engine* e) {
-  for (auto& h : e->blocks) {
-    void* ptrs[] = {h.sigma, h.accept, h.Mv, h.Mvv, h.Ls, h.nuts, h.nfr, h.width, h.sigl_d, h.hmc, h.m, h.flags,
-                    h.piv, h.xnext, h.xtag, h.astat, h.Mv_alt, h.Mvv_alt};
-    for (void* p : ptrs)
-      if (p) (void)hipFree(p);
-    h.sigma = h.accept = h.Mv = h.Mvv = h.Ls = h.nuts = h.nfr = h.width = h.sigl_d = h.hmc = nullptr;
-    h.m = h.flags = nullptr;
-    h.piv = nullptr;
-    h.xnext = nullptr;
-    h.xtag = nullptr;
-    h.astat = nullptr;
-    h.Mv_alt = h.Mvv_alt = nullptr;
-  }
-  if (e->d_vals) (void)hipFree(e->d_vals);
-  if (e->d_blocks) (void)hipFree(e->d_blocks);
-  {
-    void* lp[] = {e->lg_vec, e->lg_sc, e->lg_frames, e->lg_pos, e->lg_gpart, e->lg_lpart, e->lg_iv,
-                  e->lg_count, e->lg_itc, e->lg_s2c};
-    for (void* q : lp)
-      if (q) (void)hipFree(q);
-    e->lg_vec = e->lg_sc = e->lg_frames = e->lg_pos = e->lg_gpart = e->lg_lpart = nullptr;
-    e->lg_iv = e->lg_count = e->lg_s2c = nullptr;
-    e->lg_itc = nullptr;
-    if (e->lg_ngrad) (void)hipFree(e->lg_ngrad);
-    e->lg_ngrad = nullptr;
-    if (e->d_nstat) (void)hipFree(e->d_nstat);
-    e->d_nstat = nullptr;
-    if (e->d_cperm) (void)hipFree(e->d_cperm);
-    e->d_cperm = nullptr;
-    e->cperm_identity = true;
-    e->order_fresh = false;
-  }
-  if (e->d_draws) (void)hipFree(e->d_draws);
-  e->d_vals = nullptr;
-  e->d_blocks = nullptr;
-  e->d_draws = nullptr;
+  for (auto& h : e->blocks) static_cast<BlockChainBufs&>(h) = BlockChainBufs();
+  static_cast<ChainBufs&>(*e) = ChainBufs();
+  e->cperm_identity = true;
+  e->order_fresh = false;
   e->draws_cap = 0;
 }
-
-#ifdef MMB_PHASE_PROF
-void mmb_prof_dump();
-void mmb_prof_dump_line();
-#endif
-#ifdef MMB_WAVE_TIMES
-void mmb_wave_times_dump(int nwaves, int slots);
-void mmb_wave_times_reset(hipStream_t st);
-#endif
 
 void mmb_destroy(mmb_engine* e) {
   if (!e) return;
@@ -1182,23 +403,10 @@ void mmb_destroy(mmb_engine* e) {
   mmb_prof_dump();
   mmb_prof_dump_line();
 #endif
+  // every buffer goes here, before the streams, the events and the module
   free_dev(e);
-  if (e->d_data) (void)hipFree(e->d_data);
-  {
-    void* hp[] = {e->hpd_below, e->hpd_above, e->hpd_tmp, e->hpd_tilehist, e->hpd_words};
-    for (void* q : hp)
-      if (q) (void)hipFree(q);
-  }
-  {
-    void* ip[] = {e->d_ir_nodes, e->d_ir_code, e->d_ir_mon, e->d_ir_const, e->d_ir_pool, e->d_ir_blocks};
-    for (void* q : ip)
-      if (q) (void)hipFree(q);
-    for (BlockHost& h : e->blocks)
-      if (h.sep_d) (void)hipFree(h.sep_d);
-  }
-  if (e->lg_X) (void)hipFree(e->lg_X);
-  if (e->lg_y) (void)hipFree(e->lg_y);
-  if (e->lg_hcount) (void)hipHostFree(e->lg_hcount);
+  for (BlockHost& h : e->blocks) h.sep_d.reset();
+  static_cast<EngineBufs&>(*e) = EngineBufs();
   for (hipEvent_t ev : e->lg_cev)
     if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->lg_join)
@@ -1252,8 +460,8 @@ int mmb_set_data(mmb_engine* e, const char* name, const double* x, int64_t n) {
         hy[i] = e->y[i];
       }
       HIPCHK(e, hipSetDevice(e->device));
-      if (!e->lg_X) HIPCHK(e, hipMalloc(&e->lg_X, hx.size() * sizeof(double)));
-      if (!e->lg_y) HIPCHK(e, hipMalloc(&e->lg_y, hy.size() * sizeof(double)));
+      if (!e->lg_X) HIPCHK(e, e->lg_X.alloc(hx.size()));
+      if (!e->lg_y) HIPCHK(e, e->lg_y.alloc(hy.size()));
       HIPCHK(e, hipMemcpy(e->lg_X, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
       HIPCHK(e, hipMemcpy(e->lg_y, hy.data(), hy.size() * sizeof(double), hipMemcpyHostToDevice));
     }
@@ -1272,7 +480,7 @@ int mmb_set_data(mmb_engine* e, const char* name, const double* x, int64_t n) {
   e->have_data = !e->x.empty() && !e->y.empty();
   if (e->have_data && e->model == MMB_MODEL_RATS) {
     HIPCHK(e, hipSetDevice(e->device));
-    if (!e->d_data) HIPCHK(e, hipMalloc(&e->d_data, 150 * sizeof(double)));
+    if (!e->d_data) HIPCHK(e, e->d_data.alloc(150));
     HIPCHK(e, hipMemcpy(e->d_data, e->y.data(), 150 * sizeof(double), hipMemcpyHostToDevice));
   }
   return 0;
@@ -1291,13 +499,6 @@ int mmb_set_iter(mmb_engine* e, int64_t iter) {
   return 0;
 }
 int64_t mmb_num_kept(const mmb_engine* e) { return e ? e->n_kept : MMB_E_ARG; }
-
-int64_t mmb_tune_len(const mmb_engine* e) {
-  if (!e) return MMB_E_ARG;
-  int64_t n = 0;
-  for (auto& h : e->blocks) n += h.tune_len;
-  return n;
-}
 
 // canonical values (K x P) <-> device layout
 static void to_device_layout(const mmb_engine* e, const double* v, double* dv) {
@@ -1415,7 +616,7 @@ static int upload_blocks(mmb_engine* e) {
     d.beta = h.spec.beta;
     d.scale = h.spec.scale;
     d.width0 = h.tuning.empty() ? 0.0 : h.tuning[0];
-    d.width = (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) ? h.width : nullptr;
+    d.width = (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) ? h.width.get() : nullptr;
     d.sigl = h.sigl_d;
     d.t_sigma = h.sigma; d.t_accept = h.accept; d.t_m = h.m; d.t_flags = h.flags;
     d.t_Mv = h.Mv; d.t_Mvv = h.Mvv; d.t_Mv_alt = h.Mv_alt; d.t_Mvv_alt = h.Mvv_alt; d.t_Ls = h.Ls; d.t_piv = h.piv; d.t_xnext = h.xnext; d.t_xtag = h.xtag; d.t_nuts = h.nuts; d.t_nfr = h.nfr;
@@ -1438,16 +639,9 @@ static int upload_blocks(mmb_engine* e) {
     d.sep = h.sep_d;
     d.sep_eps = h.sep_eps;
   }
-  if (!e->d_blocks) HIPCHK(e, hipMalloc(&e->d_blocks, MMB_MAX_BLOCKS * sizeof(DBlock)));
+  if (!e->d_blocks) HIPCHK(e, e->d_blocks.alloc(MMB_MAX_BLOCKS));
   HIPCHK(e, hipMemcpy(e->d_blocks, db.data(), db.size() * sizeof(DBlock), hipMemcpyHostToDevice));
   return 0;
-}
-
-static bool amm_posform(const mmb_engine* e);
-
-template <class T>
-static hipError_t dalloc(T** p, size_t n) {
-  return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
 }
 
 int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_offset, uint64_t seed) {
@@ -1464,96 +658,96 @@ int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_
   e->seed = seed;
   e->iter = 0;
   e->n_kept = 0;
-  HIPCHK(e, dalloc(&e->d_vals, (size_t)K * e->VS));
+  HIPCHK(e, e->d_vals.alloc((size_t)K * e->VS));
   e->slice_overflows = 0;
-  HIPCHK(e, dalloc(&e->d_nstat, 8));
-  HIPCHK(e, hipMemset(e->d_nstat, 0, 8 * sizeof(unsigned long long)));
+  HIPCHK(e, e->d_nstat.alloc(8));
+  HIPCHK(e, e->d_nstat.zero(8));
   const size_t DP = e->DP, TP = e->TP;
   for (auto& h : e->blocks) {
-    HIPCHK(e, dalloc(&h.m, K));
-    HIPCHK(e, dalloc(&h.flags, K));
-    HIPCHK(e, hipMemset(h.m, 0, K * sizeof(int32_t)));
-    HIPCHK(e, hipMemset(h.flags, 0, K * sizeof(int32_t)));
+    HIPCHK(e, h.m.alloc(K));
+    HIPCHK(e, h.flags.alloc(K));
+    HIPCHK(e, h.m.zero(K));
+    HIPCHK(e, h.flags.zero(K));
     if (h.spec.sampler == MMB_SAMPLER_AMWG) {
-      HIPCHK(e, dalloc(&h.sigma, K * DP));
-      HIPCHK(e, dalloc(&h.accept, K * DP));
+      HIPCHK(e, h.sigma.alloc(K * DP));
+      HIPCHK(e, h.accept.alloc(K * DP));
       std::vector<double> sg(K * DP, 0.0);
       for (int64_t k = 0; k < K; ++k)
         for (int i = 0; i < h.d; ++i) sg[k * DP + i] = h.tuning.size() == 1 ? h.tuning[0] : h.tuning[i];
       HIPCHK(e, hipMemcpy(h.sigma, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHK(e, hipMemset(h.accept, 0, K * DP * sizeof(double)));
+      HIPCHK(e, h.accept.zero(K * DP));
     } else if (h.spec.sampler == MMB_SAMPLER_AMM) {
-      HIPCHK(e, dalloc(&h.Mv, K * DP));
-      HIPCHK(e, dalloc(&h.Mvv, K * TP));
-      HIPCHK(e, dalloc(&h.Ls, K * TP));
-      HIPCHK(e, dalloc(&h.piv, K * DP));
-      HIPCHK(e, hipMemset(h.Mv, 0, K * DP * sizeof(double)));
-      HIPCHK(e, hipMemset(h.Mvv, 0, K * TP * sizeof(double)));
-      HIPCHK(e, hipMemset(h.Ls, 0, K * TP * sizeof(double)));
+      HIPCHK(e, h.Mv.alloc(K * DP));
+      HIPCHK(e, h.Mvv.alloc(K * TP));
+      HIPCHK(e, h.Ls.alloc(K * TP));
+      HIPCHK(e, h.piv.alloc(K * DP));
+      HIPCHK(e, h.Mv.zero(K * DP));
+      HIPCHK(e, h.Mvv.zero(K * TP));
+      HIPCHK(e, h.Ls.zero(K * TP));
       if (amm_posform(e)) {  // the kernels of samplers.h amm's lazy factor store
-        HIPCHK(e, dalloc(&h.Mv_alt, K * DP));
-        HIPCHK(e, dalloc(&h.Mvv_alt, K * TP));
-        HIPCHK(e, hipMemset(h.Mv_alt, 0, K * DP * sizeof(double)));
-        HIPCHK(e, hipMemset(h.Mvv_alt, 0, K * TP * sizeof(double)));
+        HIPCHK(e, h.Mv_alt.alloc(K * DP));
+        HIPCHK(e, h.Mvv_alt.alloc(K * TP));
+        HIPCHK(e, h.Mv_alt.zero(K * DP));
+        HIPCHK(e, h.Mvv_alt.zero(K * TP));
       }
       std::vector<uint8_t> pv(K * DP);
       for (int64_t k = 0; k < K; ++k)
         for (size_t i = 0; i < DP; ++i) pv[k * DP + i] = (uint8_t)i;
       HIPCHK(e, hipMemcpy(h.piv, pv.data(), pv.size(), hipMemcpyHostToDevice));
-      HIPCHK(e, dalloc(&h.xnext, K * DP));
-      HIPCHK(e, dalloc(&h.xtag, K));
-      HIPCHK(e, hipMemset(h.xtag, 0xff, K * sizeof(int64_t)));  // -1: no carried proposal
-      HIPCHK(e, dalloc(&h.astat, K * MMB_AMM_STAT_STRIDE));
-      HIPCHK(e, hipMemset(h.astat, 0, K * MMB_AMM_STAT_STRIDE * sizeof(uint64_t)));
-      HIPCHK(e, dalloc(&h.sigl_d, (size_t)h.d * h.d));
+      HIPCHK(e, h.xnext.alloc(K * DP));
+      HIPCHK(e, h.xtag.alloc(K));
+      HIPCHK(e, h.xtag.fill_bytes(0xff, K));  // -1: no carried proposal
+      HIPCHK(e, h.astat.alloc(K * MMB_AMM_STAT_STRIDE));
+      HIPCHK(e, h.astat.zero(K * MMB_AMM_STAT_STRIDE));
+      HIPCHK(e, h.sigl_d.alloc((size_t)h.d * h.d));
       HIPCHK(e, hipMemcpy(h.sigl_d, h.sigl.data(), h.sigl.size() * sizeof(double), hipMemcpyHostToDevice));
     } else if (h.spec.sampler == MMB_SAMPLER_RWM) {
-      HIPCHK(e, dalloc(&h.sigma, K * DP));
+      HIPCHK(e, h.sigma.alloc(K * DP));
       std::vector<double> sg(K * DP, 0.0);
       for (int64_t k = 0; k < K; ++k)
         for (int i = 0; i < h.d; ++i) sg[k * DP + i] = h.tuning[i];
       HIPCHK(e, hipMemcpy(h.sigma, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHK(e, dalloc(&h.astat, K * MMB_AMM_STAT_STRIDE));
-      HIPCHK(e, hipMemset(h.astat, 0, K * MMB_AMM_STAT_STRIDE * sizeof(uint64_t)));
+      HIPCHK(e, h.astat.alloc(K * MMB_AMM_STAT_STRIDE));
+      HIPCHK(e, h.astat.zero(K * MMB_AMM_STAT_STRIDE));
     } else if (h.spec.sampler == MMB_SAMPLER_NUTS) {
-      HIPCHK(e, dalloc(&h.nuts, K * 8));
-      HIPCHK(e, hipMemset(h.nuts, 0, K * 8 * sizeof(double)));
+      HIPCHK(e, h.nuts.alloc(K * 8));
+      HIPCHK(e, h.nuts.zero(K * 8));
       if (e->model == MMB_MODEL_LINE) {
         const size_t fr = (size_t)NutsFrames<Mdl<MMB_MODEL_LINE>::G * Mdl<MMB_MODEL_LINE>::R>::DBL;
-        HIPCHK(e, dalloc(&h.nfr, K * fr));
+        HIPCHK(e, h.nfr.alloc(K * fr));
       } else if (e->model == MMB_MODEL_IR) {
         const size_t fr = (size_t)NutsFrames<Mdl<MMB_MODEL_IR>::G * Mdl<MMB_MODEL_IR>::R>::DBL;
-        HIPCHK(e, dalloc(&h.nfr, K * fr));
+        HIPCHK(e, h.nfr.alloc(K * fr));
       }
     } else if (h.spec.sampler == MMB_SAMPLER_HMC || h.spec.sampler == MMB_SAMPLER_MALA) {
-      HIPCHK(e, dalloc(&h.hmc, K * 2));
+      HIPCHK(e, h.hmc.alloc(K * 2));
       std::vector<double> t(K * 2);
       for (int64_t k = 0; k < K; ++k) { t[2 * k] = h.spec.epsilon; t[2 * k + 1] = (double)h.spec.nsteps; }
       HIPCHK(e, hipMemcpy(h.hmc, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
       if (!h.sigl.empty()) {
-        HIPCHK(e, dalloc(&h.sigl_d, (size_t)h.d * h.d));
+        HIPCHK(e, h.sigl_d.alloc((size_t)h.d * h.d));
         HIPCHK(e, hipMemcpy(h.sigl_d, h.sigl.data(), h.sigl.size() * sizeof(double), hipMemcpyHostToDevice));
       }
     } else if (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) {
-      HIPCHK(e, dalloc(&h.width, h.tuning.size()));
+      HIPCHK(e, h.width.alloc(h.tuning.size()));
       HIPCHK(e, hipMemcpy(h.width, h.tuning.data(), h.tuning.size() * sizeof(double), hipMemcpyHostToDevice));
     }
   }
   if (e->model == MMB_MODEL_LOGISTIC) {
-    HIPCHK(e, dalloc(&e->lg_vec, (size_t)K * MMB_LG_NVEC * MMB_LG_DV));
-    HIPCHK(e, hipMemset(e->lg_vec, 0, (size_t)K * MMB_LG_NVEC * MMB_LG_DV * sizeof(double)));
-    HIPCHK(e, dalloc(&e->lg_sc, (size_t)K * MMB_LG_NSC));
-    HIPCHK(e, dalloc(&e->lg_iv, (size_t)K * MMB_LG_NIV));
-    HIPCHK(e, hipMemset(e->lg_iv, 0, (size_t)K * MMB_LG_NIV * sizeof(int32_t)));
-    HIPCHK(e, dalloc(&e->lg_itc, (size_t)K));
-    HIPCHK(e, dalloc(&e->lg_frames, (size_t)K * NutsFrames<MMB_LG_DV>::DBL));
-    HIPCHK(e, dalloc(&e->lg_pos, (size_t)K * MMB_LG_DV));
-    HIPCHK(e, dalloc(&e->lg_gpart, (size_t)MMB_LG_NG * MMB_LG_NS * K * MMB_LG_DV));
-    HIPCHK(e, dalloc(&e->lg_lpart, (size_t)MMB_LG_NG * MMB_LG_NS * K * (e->lg_fd ? e->lg_p + 1 : 1)));
-    HIPCHK(e, dalloc(&e->lg_count, 2 * MMB_LG_SPLIT_MAX));
-    HIPCHK(e, dalloc(&e->lg_s2c, (size_t)2 * K));
-    HIPCHK(e, dalloc(&e->lg_ngrad, 1));
-    if (!e->lg_hcount) HIPCHK(e, hipHostMalloc(&e->lg_hcount, 2 * MMB_LG_SPLIT_MAX * sizeof(int32_t), 0));
+    HIPCHK(e, e->lg_vec.alloc((size_t)K * MMB_LG_NVEC * MMB_LG_DV));
+    HIPCHK(e, e->lg_vec.zero((size_t)K * MMB_LG_NVEC * MMB_LG_DV));
+    HIPCHK(e, e->lg_sc.alloc((size_t)K * MMB_LG_NSC));
+    HIPCHK(e, e->lg_iv.alloc((size_t)K * MMB_LG_NIV));
+    HIPCHK(e, e->lg_iv.zero((size_t)K * MMB_LG_NIV));
+    HIPCHK(e, e->lg_itc.alloc((size_t)K));
+    HIPCHK(e, e->lg_frames.alloc((size_t)K * NutsFrames<MMB_LG_DV>::DBL));
+    HIPCHK(e, e->lg_pos.alloc((size_t)K * MMB_LG_DV));
+    HIPCHK(e, e->lg_gpart.alloc((size_t)MMB_LG_NG * MMB_LG_NS * K * MMB_LG_DV));
+    HIPCHK(e, e->lg_lpart.alloc((size_t)MMB_LG_NG * MMB_LG_NS * K * (e->lg_fd ? e->lg_p + 1 : 1)));
+    HIPCHK(e, e->lg_count.alloc(2 * MMB_LG_SPLIT_MAX));
+    HIPCHK(e, e->lg_s2c.alloc((size_t)2 * K));
+    HIPCHK(e, e->lg_ngrad.alloc(1));
+    if (!e->lg_hcount) HIPCHK(e, e->lg_hcount.alloc(2 * MMB_LG_SPLIT_MAX));
     for (hipEvent_t& ev : e->lg_cev)
       if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     for (hipEvent_t& ev : e->lg_join)
@@ -1570,7 +764,7 @@ static int64_t kept_upto(int64_t t, int64_t burnin, int64_t thin) {
   return t > burnin ? (t - burnin) / thin : 0;
 }
 
-static void fill_args(const mmb_engine* e, SweepArgs& A) {
+void fill_args(const mmb_engine* e, SweepArgs& A) {
   std::memset(&A, 0, sizeof A);
   A.K = (int32_t)e->K;
   A.chain_offset = (uint32_t)e->chain_offset;
@@ -1581,7 +775,7 @@ static void fill_args(const mmb_engine* e, SweepArgs& A) {
   A.nuts_stat = e->d_nstat;
   A.ig_c = 0.001 * std::log(0.001) - std::lgamma(0.001);
   A.blocks = e->d_blocks;
-  A.cperm = e->cperm_identity ? nullptr : e->d_cperm;
+  A.cperm = e->cperm_identity ? nullptr : e->d_cperm.get();
   A.wg_offset = 0;  // one part: every workgroup (mmb_run deals them to parts)
   A.wg_stride = 1;
   {  // MMB_AMWG_EXACT=1: AMWG updates by amwg_sub!'s sequential loop; 2: wide AMWG band.
@@ -1686,17 +880,6 @@ static int iters_per_launch(const mmb_engine* e, int parts, int64_t iters) {
   return W;
 }
 
-template <class T>
-static int d2h(mmb_engine* e, std::vector<T>& h, const T* d, size_t n) {
-  h.resize(n);
-  HIPCHK(e, hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost));
-  return 0;
-}
-template <class T>
-static int h2d(mmb_engine* e, T* d, const std::vector<T>& h) {
-  HIPCHK(e, hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
 
 // Wavefront pairing of the 32-lane kernels (two chains per wavefront step together): a chain whose
 // AMM moment matrix is indefinite stops its pivoted Cholesky after a few pivots every update
@@ -1719,7 +902,7 @@ static int order_chains(mmb_engine* e) {
   for (const BlockHost& h : e->blocks)
     if (h.spec.sampler == MMB_SAMPLER_AMM && h.flags && oa.nblk < MMB_ORDER_BLOCKS) oa.flags[oa.nblk++] = h.flags;
   if (oa.nblk == 0) return 0;
-  if (!e->d_cperm) HIPCHK(e, dalloc(&e->d_cperm, (size_t)e->K));
+  if (!e->d_cperm) HIPCHK(e, e->d_cperm.alloc((size_t)e->K));
   oa.K = (int32_t)e->K;
   oa.perm = e->d_cperm;
   // chains per workgroup of the 32-lane sweep kernels (sweep.hip launch: rats 256 threads, node IR 128)
@@ -1786,7 +969,7 @@ static int run_logistic(mmb_engine* e, const mmb_run_args* a, double* draws, int
   A0.vals = e->d_vals; A0.vec = e->lg_vec; A0.sc = e->lg_sc; A0.iv = e->lg_iv; A0.itc = e->lg_itc;
   A0.kind = h.spec.sampler;
   A0.frames = e->lg_frames; A0.tm = h.m; A0.tflags = h.flags;
-  A0.tune = A0.kind == MMB_SAMPLER_NUTS ? h.nuts : h.hmc;
+  A0.tune = A0.kind == MMB_SAMPLER_NUTS ? h.nuts.get() : h.hmc.get();
   const int tune_w = A0.kind == MMB_SAMPLER_NUTS ? 8 : 2;
   A0.sigl = h.sigl_d;
   A0.draws = draws;
@@ -1970,13 +1153,12 @@ int mmb_run(mmb_engine* e, const mmb_run_args* a) {
   if (want && nk > 0) {
     size_t need = (size_t)nk * e->pmon * e->K;
     if (need > e->draws_cap) {
-      if (e->d_draws) HIPCHK(e, hipFree(e->d_draws));
-      e->d_draws = nullptr;
-      HIPCHK(e, dalloc(&e->d_draws, need));
+      e->draws_cap = 0;
+      HIPCHK(e, e->d_draws.alloc(need));
       e->draws_cap = need;
     }
   }
-  if (e->model == MMB_MODEL_LOGISTIC) return run_logistic(e, a, (want && nk > 0) ? e->d_draws : nullptr, kept0, nk, want);
+  if (e->model == MMB_MODEL_LOGISTIC) return run_logistic(e, a, (want && nk > 0) ? e->d_draws.get() : nullptr, kept0, nk, want);
   if (a->iters > 0 && !e->order_fresh) {  // else computed right after a previous window
     int orc = order_chains(e);
     if (orc) return orc;
@@ -1988,7 +1170,7 @@ int mmb_run(mmb_engine* e, const mmb_run_args* a) {
   A.thin = a->thin;
   A.model_burnin = a->model_burnin;
   A.kept_origin = kept0;
-  A.draws = (want && nk > 0) ? e->d_draws : nullptr;
+  A.draws = (want && nk > 0) ? e->d_draws.get() : nullptr;
   int np = 1;
   {
     int rc = sweep_parts(e, A, &np);
@@ -2145,11 +1327,9 @@ int mmb_reserve_draws(mmb_engine* e, int64_t nkept) {
   if (need > e->draws_cap) {
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));  // the old buffer may still be read by a kernel
-    if (e->d_draws) HIPCHK(e, hipFree(e->d_draws));
-    e->d_draws = nullptr;
     e->draws_cap = 0;
     e->n_kept = 0;  // the kept draws (if any) went with the old buffer
-    HIPCHK(e, dalloc(&e->d_draws, need));
+    HIPCHK(e, e->d_draws.alloc(need));
     e->draws_cap = need;
   }
   return 0;
@@ -2186,908 +1366,6 @@ int mmb_set_draws(mmb_engine* e, const double* draws, int64_t nkept) {
   HIPCHK(e, hipMemcpyAsync(e->d_draws, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   e->n_kept = nkept;
-  return 0;
-}
-
-// ---------------------------------------------------------------- tune (canonical layout)
-
-// The 32-lane factorization (samplers.h pchol32: rats, node IR) keeps the AMM factor in
-// POSITION form on device -- row at pivot position t at tri(t) + k, k = 0..t, plus one byte per
-// element holding its position -- while the canonical tune layout (and the oracle) use the slot
-// form L[e][step k] -> slot(e, piv[k]), diagonal at slot(e, e), plus the pivot order.
-static bool amm_posform(const mmb_engine* e) { return e->model == MMB_MODEL_RATS || e->model == MMB_MODEL_IR; }
-static int tri_(int i) { return i * (i + 1) / 2; }
-static int slot_(int i, int k) { return i >= k ? tri_(i) + k : tri_(k) + i; }
-// position form (lp, pos) -> slot form (ls, piv); one chain, d x d
-static void pos_to_slot(int d, const double* lp, const uint8_t* pos, double* ls, uint8_t* piv) {
-  for (int e = 0; e < d; ++e) piv[pos[e] < d ? pos[e] : e] = (uint8_t)e;
-  for (int e = 0; e < d; ++e) {
-    const int pe = pos[e] < d ? pos[e] : e;
-    for (int k = 0; k < pe; ++k) ls[slot_(e, piv[k])] = lp[tri_(pe) + k];
-    ls[slot_(e, e)] = lp[tri_(pe) + pe];
-  }
-}
-static void slot_to_pos(int d, const double* ls, const uint8_t* piv, double* lp, uint8_t* pos) {
-  for (int k = 0; k < d; ++k) pos[piv[k] < d ? piv[k] : k] = (uint8_t)k;
-  for (int e = 0; e < d; ++e) {
-    const int pe = pos[e];
-    for (int k = 0; k < pe; ++k) lp[tri_(pe) + k] = ls[slot_(e, piv[k])];
-    lp[tri_(pe) + pe] = ls[slot_(e, e)];
-  }
-}
-
-int mmb_get_tune(mmb_engine* e, double* tune) {
-  if (!e || !tune) return fail(e, MMB_E_ARG, "null argument");
-  if (!e->d_vals) return fail(e, MMB_E_STATE, "mmb_init_chains not called");
-  HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  const int64_t TL = mmb_tune_len(e), K = e->K;
-  const size_t DP = e->DP, TP = e->TP;
-  int64_t off = 0;
-  for (auto& h : e->blocks) {
-    std::vector<int32_t> m, fl;
-    int rc;
-    if ((rc = d2h(e, m, h.m, K)) || (rc = d2h(e, fl, h.flags, K))) return rc;
-    if (h.spec.sampler == MMB_SAMPLER_AMWG) {
-      std::vector<double> sg, ac;
-      if ((rc = d2h(e, sg, h.sigma, K * DP)) || (rc = d2h(e, ac, h.accept, K * DP))) return rc;
-      for (int64_t k = 0; k < K; ++k) {
-        double* t = tune + k * TL + off;
-        t[0] = (fl[k] & 1) ? 1.0 : 0.0;
-        t[1] = m[k];
-        for (int i = 0; i < h.d; ++i) { t[2 + i] = sg[k * DP + i]; t[2 + h.d + i] = ac[k * DP + i]; }
-      }
-    } else if (h.spec.sampler == MMB_SAMPLER_AMM) {
-      std::vector<double> mv, mvv, ls;
-      std::vector<uint8_t> pv;
-      if ((rc = d2h(e, mv, h.Mv, K * DP)) || (rc = d2h(e, mvv, h.Mvv, K * TP)) ||
-          (rc = d2h(e, ls, h.Ls, K * TP)) || (rc = d2h(e, pv, h.piv, K * DP)))
-        return rc;
-      if (h.Mv_alt) {  // two moment buffers: chain k's current ones are those of m[k]'s parity
-        std::vector<double> mva, mvva;
-        if ((rc = d2h(e, mva, h.Mv_alt, K * DP)) || (rc = d2h(e, mvva, h.Mvv_alt, K * TP))) return rc;
-        for (int64_t k = 0; k < K; ++k) {
-          if (!(m[k] & 1)) continue;
-          std::copy(&mva[k * DP], &mva[k * DP] + DP, &mv[k * DP]);
-          std::copy(&mvva[k * TP], &mvva[k * TP] + TP, &mvv[k * TP]);
-        }
-      }
-      for (int64_t k = 0; k < K; ++k) {
-        double* t = tune + k * TL + off;
-        t[0] = (fl[k] & 1) ? 1.0 : 0.0;
-        t[1] = m[k];
-        t[2] = (fl[k] & 4) ? 1.0 : 0.0;
-        t[3] = (fl[k] & 2) ? 1.0 : 0.0;
-        double* p = t + 4;
-        for (int i = 0; i < h.d; ++i) p[i] = mv[k * DP + i];
-        p += h.d;
-        for (int s = 0; s < h.T; ++s) p[s] = mvv[k * TP + s];
-        p += h.T;
-        if (amm_posform(e)) {
-          std::vector<uint8_t> piv(h.d);
-          std::fill(p, p + h.T, 0.0);
-          pos_to_slot(h.d, &ls[k * TP], &pv[k * DP], p, piv.data());
-          p += h.T;
-          for (int i = 0; i < h.d; ++i) p[i] = piv[i];
-        } else {
-          for (int s = 0; s < h.T; ++s) p[s] = ls[k * TP + s];
-          p += h.T;
-          for (int i = 0; i < h.d; ++i) p[i] = pv[k * DP + i];
-        }
-      }
-    } else if (h.spec.sampler == MMB_SAMPLER_NUTS) {
-      std::vector<double> nt;
-      if ((rc = d2h(e, nt, h.nuts, K * 8))) return rc;
-      for (int64_t k = 0; k < K; ++k) {  // [adapt, m, eps, epsbar, Hbar, mu, alpha, nalpha, init]
-        double* t = tune + k * TL + off;
-        t[0] = (fl[k] & 1) ? 1.0 : 0.0;
-        t[1] = m[k];
-        for (int i = 0; i < 6; ++i) t[2 + i] = nt[k * 8 + i];
-        t[8] = (fl[k] & 8) ? 1.0 : 0.0;
-      }
-    } else if (h.spec.sampler == MMB_SAMPLER_HMC || h.spec.sampler == MMB_SAMPLER_MALA) {
-      std::vector<double> th;
-      if ((rc = d2h(e, th, h.hmc, K * 2))) return rc;
-      for (int64_t k = 0; k < K; ++k)
-        for (int i = 0; i < h.tune_len; ++i) tune[k * TL + off + i] = th[k * 2 + i];
-    } else if (h.spec.sampler == MMB_SAMPLER_RWM) {
-      std::vector<double> sg;
-      if ((rc = d2h(e, sg, h.sigma, K * DP))) return rc;
-      for (int64_t k = 0; k < K; ++k)
-        for (int i = 0; i < h.d; ++i) tune[k * TL + off + i] = sg[k * DP + i];
-    }
-    off += h.tune_len;
-  }
-  return 0;
-}
-
-int mmb_set_tune(mmb_engine* e, const double* tune) {
-  if (!e || !tune) return fail(e, MMB_E_ARG, "null argument");
-  if (!e->d_vals) return fail(e, MMB_E_STATE, "mmb_init_chains not called");
-  const int64_t TL = mmb_tune_len(e), K = e->K;
-  const size_t DP = e->DP, TP = e->TP;
-  // validate every row before any device state changes: a valid AMM factor (t[2] != 0) needs
-  // its pivot order to be a permutation of 0..d-1 (it indexes the caller's row and the device
-  // factor); an invalid one is stored with identity positions whatever its pivot bytes hold
-  for (int64_t off = 0, b = 0; b < (int64_t)e->blocks.size(); off += e->blocks[b].tune_len, ++b) {
-    const auto& h = e->blocks[b];
-    if (h.spec.sampler != MMB_SAMPLER_AMM) continue;
-    for (int64_t k = 0; k < K; ++k) {
-      const double* t = tune + k * TL + off;
-      if (t[2] == 0.0) continue;
-      const double* pv = t + 4 + h.d + 2 * h.T;
-      uint32_t seen = 0;
-      for (int i = 0; i < h.d; ++i) {
-        const double v = pv[i];
-        if (!(v >= 0.0 && v < h.d) || v != (double)(int)v || (seen >> (int)v & 1u))
-          return fail(e, MMB_E_ARG, "block %d chain %lld: AMM pivot order is not a permutation of 0..%d",
-                      (int)b + 1, (long long)k, h.d - 1);
-        seen |= 1u << (int)v;
-      }
-    }
-  }
-  ++e->xepoch;
-  e->order_fresh = false;  // the factor-valid flags change
-  HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  int64_t off = 0;
-  for (auto& h : e->blocks) {
-    std::vector<int32_t> m(K, 0), fl(K, 0);
-    int rc;
-    if (h.spec.sampler == MMB_SAMPLER_AMWG) {
-      std::vector<double> sg(K * DP, 0.0), ac(K * DP, 0.0);
-      for (int64_t k = 0; k < K; ++k) {
-        const double* t = tune + k * TL + off;
-        fl[k] = t[0] != 0.0 ? 1 : 0;
-        m[k] = (int32_t)t[1];
-        for (int i = 0; i < h.d; ++i) { sg[k * DP + i] = t[2 + i]; ac[k * DP + i] = t[2 + h.d + i]; }
-      }
-      if ((rc = h2d(e, h.sigma, sg)) || (rc = h2d(e, h.accept, ac))) return rc;
-    } else if (h.spec.sampler == MMB_SAMPLER_AMM) {
-      std::vector<double> mv(K * DP, 0.0), mvv(K * TP, 0.0), ls(K * TP, 0.0);
-      std::vector<uint8_t> pv(K * DP, 0);
-      for (int64_t k = 0; k < K; ++k) {
-        const double* t = tune + k * TL + off;
-        fl[k] = (t[0] != 0.0 ? 1 : 0) | (t[2] != 0.0 ? 4 : 0) | (t[3] != 0.0 ? 2 : 0);
-        m[k] = (int32_t)t[1];
-        const double* p = t + 4;
-        for (int i = 0; i < h.d; ++i) mv[k * DP + i] = p[i];
-        p += h.d;
-        for (int s = 0; s < h.T; ++s) mvv[k * TP + s] = p[s];
-        p += h.T;
-        const bool valid = t[2] != 0.0;
-        if (amm_posform(e)) {
-          std::vector<uint8_t> piv(h.d);
-          for (int i = 0; i < h.d; ++i) piv[i] = valid ? (uint8_t)p[h.T + i] : (uint8_t)i;
-          slot_to_pos(h.d, p, piv.data(), &ls[k * TP], &pv[k * DP]);
-        } else {
-          for (int s = 0; s < h.T; ++s) ls[k * TP + s] = p[s];
-          p += h.T;
-          for (int i = 0; i < h.d; ++i) pv[k * DP + i] = valid ? (uint8_t)p[i] : (uint8_t)i;
-        }
-      }
-      if ((rc = h2d(e, h.Mv, mv)) || (rc = h2d(e, h.Mvv, mvv)) || (rc = h2d(e, h.Ls, ls)) ||
-          (rc = h2d(e, h.piv, pv)))
-        return rc;
-      // two moment buffers: both get the row, so the one of the chain's m holds it
-      if (h.Mv_alt && ((rc = h2d(e, h.Mv_alt, mv)) || (rc = h2d(e, h.Mvv_alt, mvv)))) return rc;
-    } else if (h.spec.sampler == MMB_SAMPLER_NUTS) {
-      std::vector<double> nt(K * 8, 0.0);
-      for (int64_t k = 0; k < K; ++k) {
-        const double* t = tune + k * TL + off;
-        fl[k] = (t[0] != 0.0 ? 1 : 0) | (t[8] != 0.0 ? 8 : 0);
-        m[k] = (int32_t)t[1];
-        for (int i = 0; i < 6; ++i) nt[k * 8 + i] = t[2 + i];
-      }
-      if ((rc = h2d(e, h.nuts, nt))) return rc;
-    } else if (h.spec.sampler == MMB_SAMPLER_HMC || h.spec.sampler == MMB_SAMPLER_MALA) {
-      std::vector<double> th(K * 2);
-      for (int64_t k = 0; k < K; ++k) {
-        const double* t = tune + k * TL + off;
-        th[k * 2] = t[0];
-        th[k * 2 + 1] = h.tune_len > 1 ? t[1] : (double)h.spec.nsteps;
-      }
-      if ((rc = h2d(e, h.hmc, th))) return rc;
-    } else if (h.spec.sampler == MMB_SAMPLER_RWM) {
-      std::vector<double> sg(K * DP, 0.0);
-      for (int64_t k = 0; k < K; ++k)
-        for (int i = 0; i < h.d; ++i) sg[k * DP + i] = tune[k * TL + off + i];
-      if ((rc = h2d(e, h.sigma, sg))) return rc;
-    }
-    if ((rc = h2d(e, h.m, m)) || (rc = h2d(e, h.flags, fl))) return rc;
-    off += h.tune_len;
-  }
-  return 0;
-}
-
-// ---------------------------------------------------------------- Gelman-Rubin partials
-int64_t mmb_gr_len(const mmb_engine* e) {
-  if (!e) return MMB_E_ARG;
-  const int64_t p = e->pmon;
-  return 1 + p + p * p + p * p + 3 * p;
-}
-
-int mmb_gr_range(mmb_engine* e, double* minmax) {
-  if (!e || !minmax) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  HIPCHK(e, hipSetDevice(e->device));
-  double* d = nullptr;
-  HIPCHK(e, hipMalloc(&d, 2 * e->pmon * sizeof(double)));
-  hipError_t st = mmb_launch_gr_range(e->pmon, e->n_kept, (int)e->K, e->d_draws, d, e->stream);
-  if (st != hipSuccess) { (void)hipFree(d); return fail(e, MMB_E_HIP, "gr_range: %s", hipGetErrorString(st)); }
-  HIPCHK(e, hipMemcpyAsync(minmax, d, 2 * e->pmon * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipFree(d));
-  return 0;
-}
-
-// gr.hip holds a chain's p x p covariance in thread-owned pairs: p <= mmb_gr_pmax()
-static int gr_width_check(mmb_engine* e) {
-  if (e->pmon > mmb_gr_pmax())
-    return fail(e, MMB_E_UNSUPPORTED, "Gelman-Rubin sums (gelmandiag, cor) serve at most %d monitored values; "
-                "this model monitors %d", mmb_gr_pmax(), e->pmon);
-  return 0;
-}
-
-int mmb_gr_partials(mmb_engine* e, const int32_t* link, const double* shift, double* out) {
-  if (!e || !link || !shift || !out) return fail(e, MMB_E_ARG, "null argument");
-  if (int rc = gr_width_check(e)) return rc;
-  if (e->n_kept < 2) return fail(e, MMB_E_STATE, "need >= 2 device-kept draws per chain");
-  HIPCHK(e, hipSetDevice(e->device));
-  const int p = e->pmon;
-  const int64_t L = mmb_gr_len(e);
-  int32_t* dl = nullptr;
-  double *ds = nullptr, *dout = nullptr;
-  HIPCHK(e, hipMalloc(&dl, p * sizeof(int32_t)));
-  HIPCHK(e, hipMalloc(&ds, p * sizeof(double)));
-  HIPCHK(e, hipMalloc(&dout, L * sizeof(double)));
-  HIPCHK(e, hipMemcpyAsync(dl, link, p * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipMemcpyAsync(ds, shift, p * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  hipError_t st = mmb_launch_gr_stats(p, e->n_kept, (int)e->K, e->d_draws, dl, ds, dout, e->stream);
-  if (st != hipSuccess) {
-    (void)hipFree(dl);
-    (void)hipFree(ds);
-    (void)hipFree(dout);
-    return fail(e, MMB_E_HIP, "gr_stats: %s", hipGetErrorString(st));
-  }
-  HIPCHK(e, hipMemcpyAsync(out, dout, L * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  (void)hipFree(dl);
-  (void)hipFree(ds);
-  (void)hipFree(dout);
-  return 0;
-}
-
-// ---------------------------------------------------------------- posterior summaries
-int mmb_chain_summary(mmb_engine* e, const double* shift, int64_t batch_size, int64_t chain_base, double* out) {
-  if (!e || !shift || !out) return fail(e, MMB_E_ARG, "null argument");
-  if (batch_size < 1) return fail(e, MMB_E_ARG, "batch size must be positive");
-  if (chain_base < 0) return fail(e, MMB_E_ARG, "chain_base must be >= 0");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  HIPCHK(e, hipSetDevice(e->device));
-  const int p = e->pmon;
-  const size_t nout = (size_t)e->K * p * MMB_SUMMARY_FIELDS;
-  double *ds = nullptr, *dout = nullptr;
-  HIPCHK(e, hipMalloc(&ds, p * sizeof(double)));
-  HIPCHK(e, hipMalloc(&dout, nout * sizeof(double)));
-  HIPCHK(e, hipMemcpyAsync(ds, shift, p * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  hipError_t st = mmb_launch_chain_summary(p, e->n_kept, (int)e->K, chain_base, batch_size, e->d_draws, ds,
-                                           dout, e->stream);
-  if (st == hipSuccess) st = hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  (void)hipFree(ds);
-  (void)hipFree(dout);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "chain_summary: %s", hipGetErrorString(st));
-  return 0;
-}
-
-int mmb_order_hist(mmb_engine* e, int param, int ntargets, const uint64_t* prefix, int pass, uint64_t* counts) {
-  if (!e || !prefix || !counts) return fail(e, MMB_E_ARG, "null argument");
-  if (param < 0 || param >= e->pmon) return fail(e, MMB_E_ARG, "param %d out of range", param);
-  if (ntargets < 1 || ntargets > MMB_ORDER_MAX_TARGETS) return fail(e, MMB_E_ARG, "1 <= ntargets <= %d",
-                                                                      MMB_ORDER_MAX_TARGETS);
-  if (pass < 0 || pass > 7) return fail(e, MMB_E_ARG, "pass must be 0..7");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  HIPCHK(e, hipSetDevice(e->device));
-  uint64_t* dp = nullptr;
-  unsigned long long* dc = nullptr;
-  HIPCHK(e, hipMalloc(&dp, ntargets * sizeof(uint64_t)));
-  HIPCHK(e, hipMalloc(&dc, (size_t)ntargets * 256 * sizeof(unsigned long long)));
-  hipError_t st = hipMemcpyAsync(dp, prefix, ntargets * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream);
-  if (st == hipSuccess)
-    st = mmb_launch_order_hist(e->pmon, param, e->n_kept, (int)e->K, e->d_draws, ntargets, dp, pass, dc, e->stream);
-  if (st == hipSuccess)
-    st = hipMemcpyAsync(counts, dc, (size_t)ntargets * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  (void)hipFree(dp);
-  (void)hipFree(dc);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "order_hist: %s", hipGetErrorString(st));
-  return 0;
-}
-
-// ---------------------------------------------------------------- hpd (stats.jl:54-74)
-// hpd_words: the collect pass's counts and key bits, the sort's digit totals, the gap's partials and result
-constexpr int HPD_W_META = 0, HPD_W_GHIST = 8, HPD_W_PARTD = 264, HPD_W_PARTI = 520, HPD_W_RES = 776,
-              HPD_WORDS = 784;
-constexpr int64_t HPD_MAX_KEYS = 0xffffffffll;  // the sort's scatter offsets are 32-bit
-
-// room for `cap` keys in each tail and in the sort buffer; growing drops the tails held
-static int hpd_reserve(mmb_engine* e, int64_t cap) {
-  HIPCHK(e, hipSetDevice(e->device));
-  if (!e->hpd_words) HIPCHK(e, dalloc(&e->hpd_words, (size_t)HPD_WORDS));
-  if (cap <= e->hpd_cap) return 0;
-  HIPCHK(e, hipStreamSynchronize(e->stream));  // the old buffers may still be read by a kernel
-  void* old[] = {e->hpd_below, e->hpd_above, e->hpd_tmp, e->hpd_tilehist};
-  for (void* q : old)
-    if (q) (void)hipFree(q);
-  e->hpd_below = e->hpd_above = e->hpd_tmp = nullptr;
-  e->hpd_tilehist = nullptr;
-  e->hpd_cap = 0;
-  e->hpd_have = false;
-  hipError_t st = dalloc(&e->hpd_below, (size_t)cap);
-  if (st == hipSuccess) st = dalloc(&e->hpd_above, (size_t)cap);
-  if (st == hipSuccess) st = dalloc(&e->hpd_tmp, (size_t)cap);
-  if (st == hipSuccess) st = dalloc(&e->hpd_tilehist, (size_t)256 * mmb_hpd_tiles(cap));
-  if (st != hipSuccess)
-    return fail(e, st == hipErrorOutOfMemory ? MMB_E_NOMEM : MMB_E_HIP, "hpd buffers for %lld values: %s",
-                (long long)cap, hipGetErrorString(st));
-  e->hpd_cap = cap;
-  return 0;
-}
-
-int mmb_hpd_collect(mmb_engine* e, int param, double lo, double hi, int64_t cap, int64_t counts[2]) {
-  if (!e || !counts) return fail(e, MMB_E_ARG, "null argument");
-  if (param < 0 || param >= e->pmon) return fail(e, MMB_E_ARG, "param %d out of range", param);
-  if (cap < 0 || cap > HPD_MAX_KEYS) return fail(e, MMB_E_ARG, "cap must be 0 .. %lld", (long long)HPD_MAX_KEYS);
-  if (lo != lo || hi != hi) return fail(e, MMB_E_ARG, "a threshold is NaN");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  e->hpd_have = e->hpd_sorted = false;
-  if (int rc = hpd_reserve(e, cap)) return rc;
-  unsigned long long* meta = e->hpd_words + HPD_W_META;
-  unsigned long long h[6] = {};
-  hipError_t st = mmb_launch_hpd_collect(e->pmon, param, e->n_kept, (int)e->K, e->d_draws, lo, hi, cap, e->hpd_below,
-                                         e->hpd_above, meta, e->stream);
-  if (st == hipSuccess) st = hipMemcpyAsync(h, meta, sizeof h, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_collect: %s", hipGetErrorString(st));
-  counts[0] = (int64_t)h[0];
-  counts[1] = (int64_t)h[1];
-  if (counts[0] > cap || counts[1] > cap)
-    return fail(e, MMB_E_ARG, "hpd_collect: %lld draws below lo and %lld above hi, room for %lld each (lo and hi "
-                "must be the order statistics m - 1 and N - m, cap = m - 1)", (long long)counts[0],
-                (long long)counts[1], (long long)cap);
-  for (int b = 0; b < 2; ++b) {
-    e->hpd_n[b] = counts[b];
-    e->hpd_varying[b] = counts[b] > 0 ? (uint64_t)(h[2 + 2 * b] ^ h[3 + 2 * b]) : 0;
-  }
-  e->hpd_have = true;
-  return 0;
-}
-
-int mmb_hpd_get_tails(mmb_engine* e, double* below, int64_t nbelow, double* above, int64_t nabove) {
-  if (!e || (nbelow > 0 && !below) || (nabove > 0 && !above)) return fail(e, MMB_E_ARG, "null argument");
-  if (nbelow < 0 || nabove < 0) return fail(e, MMB_E_ARG, "counts must be >= 0");
-  if (nbelow > e->hpd_cap || nabove > e->hpd_cap)
-    return fail(e, MMB_E_ARG, "counts %lld, %lld exceed the tail buffers' %lld", (long long)nbelow, (long long)nabove,
-                (long long)e->hpd_cap);
-  if (nbelow + nabove == 0) return 0;
-  HIPCHK(e, hipSetDevice(e->device));
-  std::vector<uint64_t> kb((size_t)nbelow), ka((size_t)nabove);
-  hipError_t st = hipSuccess;
-  if (nbelow > 0)
-    st = hipMemcpyAsync(kb.data(), e->hpd_below, kb.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess && nabove > 0)
-    st = hipMemcpyAsync(ka.data(), e->hpd_above, ka.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_get_tails: %s", hipGetErrorString(st));
-  for (int64_t i = 0; i < nbelow; ++i) below[i] = mmb_hpd_unkey(kb[(size_t)i]);
-  for (int64_t i = 0; i < nabove; ++i) above[i] = mmb_hpd_unkey(ka[(size_t)i]);
-  return 0;
-}
-
-int mmb_hpd_set_tails(mmb_engine* e, const double* below, int64_t nbelow, const double* above, int64_t nabove) {
-  if (!e || (nbelow > 0 && !below) || (nabove > 0 && !above)) return fail(e, MMB_E_ARG, "null argument");
-  if (nbelow < 0 || nabove < 0) return fail(e, MMB_E_ARG, "counts must be >= 0");
-  if (nbelow > HPD_MAX_KEYS || nabove > HPD_MAX_KEYS)
-    return fail(e, MMB_E_ARG, "at most %lld values per tail", (long long)HPD_MAX_KEYS);
-  e->hpd_have = e->hpd_sorted = false;
-  if (int rc = hpd_reserve(e, std::max(nbelow, nabove))) return rc;
-  const double* src[2] = {below, above};
-  const int64_t cnt[2] = {nbelow, nabove};
-  uint64_t* dst[2] = {e->hpd_below, e->hpd_above};
-  std::vector<uint64_t> keys[2];
-  hipError_t st = hipSuccess;
-  for (int b = 0; b < 2 && st == hipSuccess; ++b) {
-    keys[b].resize((size_t)cnt[b]);
-    uint64_t bor = 0, band = ~0ull;
-    for (int64_t i = 0; i < cnt[b]; ++i) {
-      const uint64_t k = mmb_hpd_key(src[b][i]);
-      keys[b][(size_t)i] = k;
-      bor |= k;
-      band &= k;
-    }
-    e->hpd_varying[b] = cnt[b] > 0 ? bor ^ band : 0;
-    if (cnt[b] > 0)
-      st = hipMemcpyAsync(dst[b], keys[b].data(), keys[b].size() * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream);
-  }
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);  // the host copies go out of scope
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_set_tails: %s", hipGetErrorString(st));
-  e->hpd_n[0] = nbelow;
-  e->hpd_n[1] = nabove;
-  e->hpd_have = true;
-  return 0;
-}
-
-int mmb_hpd_gap(mmb_engine* e, int64_t m, int64_t total, double lo, double hi, double out[2], int64_t* index) {
-  if (!e || !out || !index) return fail(e, MMB_E_ARG, "null argument");
-  if (m < 1 || m > total) return fail(e, MMB_E_ARG, "need 1 <= m <= total, got m = %lld, total = %lld", (long long)m,
-                                      (long long)total);
-  if (lo != lo || hi != hi) return fail(e, MMB_E_ARG, "a threshold is NaN");
-  if (lo > hi && m <= total - m)
-    return fail(e, MMB_E_ARG, "lo = %g > hi = %g although the tails do not overlap (2 m <= total)", lo, hi);
-  if (!e->hpd_have) return fail(e, MMB_E_STATE, "no tails: call mmb_hpd_collect or mmb_hpd_set_tails first");
-  if (e->hpd_n[0] > m - 1 || e->hpd_n[1] > m - 1)
-    return fail(e, MMB_E_ARG, "the tails hold %lld and %lld values, more than m - 1 = %lld", (long long)e->hpd_n[0],
-                (long long)e->hpd_n[1], (long long)(m - 1));
-  HIPCHK(e, hipSetDevice(e->device));
-  hipError_t st = hipSuccess;
-  if (!e->hpd_sorted) {
-    uint64_t** buf[2] = {&e->hpd_below, &e->hpd_above};
-    for (int b = 0; b < 2 && st == hipSuccess; ++b) {
-      int in_tmp = 0;
-      st = mmb_launch_hpd_sort(*buf[b], e->hpd_tmp, e->hpd_n[b], e->hpd_varying[b], e->hpd_tilehist,
-                               e->hpd_words + HPD_W_GHIST, &in_tmp, e->stream);
-      if (st == hipSuccess && in_tmp) std::swap(*buf[b], e->hpd_tmp);  // equal capacities: the buffers trade places
-    }
-    if (st != hipSuccess) {
-      e->hpd_have = false;  // a buffer may be half sorted
-      return fail(e, MMB_E_HIP, "hpd sort: %s", hipGetErrorString(st));
-    }
-    e->hpd_sorted = true;
-  }
-  unsigned long long h[3] = {};
-  double* res = (double*)(e->hpd_words + HPD_W_RES);
-  st = mmb_launch_hpd_gap(e->hpd_below, e->hpd_n[0], e->hpd_above, e->hpd_n[1], m, lo, hi,
-                          (double*)(e->hpd_words + HPD_W_PARTD), (long long*)(e->hpd_words + HPD_W_PARTI), res,
-                          e->stream);
-  if (st == hipSuccess) st = hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "hpd_gap: %s", hipGetErrorString(st));
-  memcpy(out, h, 2 * sizeof(double));
-  *index = (int64_t)h[2];
-  return 0;
-}
-
-// ---------------------------------------------------------------- model statistics (modelstats.jl)
-// The plan of a node list: validated ids and, for node-IR models, the monitored columns to load and the
-// state slots they fill.  getsimkeys (modelstats.jl:107-132) relists the sampled nodes the requested nodes
-// depend on through Logicals; here that is the read set of their parameter expressions (Logicals are
-// inlined): the VAL / VALI / VALG words over every element, VALG through the gather indices in the pool.
-struct MsPlan {
-  std::vector<int32_t> col, slot;
-};
-
-static int ms_plan(mmb_engine* e, int nnodes, const int32_t* nodes, bool need_draws, MsPlan& pl,
-                   const char* what = "logpdf") {
-  if (e->model == MMB_MODEL_RATS)
-    return fail(e, MMB_E_UNSUPPORTED, "%s: the hand-lowered rats model monitors 3 of its 65 values (s2_c, mu_beta, "
-                "alpha0): alpha and beta are not in the chains, so the nodes cannot be relisted from the draws "
-                "(use the node-IR rats model with alpha, beta and the hyper-parameters monitored)", what);
-  if (e->model == MMB_MODEL_LOGISTIC)
-    return fail(e, MMB_E_UNSUPPORTED, "%s: the logistic model evaluates its likelihood through its own batched "
-                "engine; its model statistics are not lowered yet", what);
-  if (!e->d_vals || (need_draws && e->n_kept < 1))
-    return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  if (nnodes < 1 || nnodes > MMB_IR_MAX_TERMS) return fail(e, MMB_E_ARG, "1 <= nnodes <= %d", MMB_IR_MAX_TERMS);
-  if (e->model == MMB_MODEL_LINE) {
-    for (int a = 0; a < nnodes; ++a)
-      if (nodes[a] < 0 || nodes[a] > MMB_LINE_Y)
-        return fail(e, MMB_E_ARG, "node id %d is not a Stochastic node of the line model", nodes[a]);
-    return 0;
-  }
-  const int NN = (int)e->ir_nodes.size();
-  std::vector<int> colstart(NN, -1);  // first monitored column of a node, -1: not monitored
-  int c0 = 0;
-  for (int32_t nid : e->ir_mon) {
-    colstart[nid] = c0;
-    c0 += e->ir_nodes[nid].len;
-  }
-  auto sampled = [&](const mmb_ir_node& N) { return !N.fixed && N.family != MMB_IR_LOGICAL; };
-  std::vector<char> need(NN, 0);
-  for (int a = 0; a < nnodes; ++a) {
-    const int nid = nodes[a];
-    if (nid < 0 || nid >= NN || e->ir_nodes[nid].family == MMB_IR_LOGICAL)
-      return fail(e, MMB_E_ARG, "node id %d is not a Stochastic node of the model", nid);
-    const mmb_ir_node& N = e->ir_nodes[nid];
-    if (sampled(N)) need[nid] = 1;
-    std::vector<int> slots;
-    if (const int po = mmb_ir_cat_state(N.family, N.cterm); po >= 0)  // Categorical(P) reads P's slots
-      for (int i = 0; i < (int)N.hi; ++i) slots.push_back(po + i);
-    for (int k = 0; k < 3; ++k) {
-      if (N.expr[k] < 0) continue;
-      const int ne = (N.family == MMB_IR_ISONORMAL && k == 1) ? 1 : N.len;
-      for (int i = 0; i < ne; ++i) ir_expr_slots(e->ir_code, e->ir_pool, N.expr[k], i, slots);
-    }
-    for (int s : slots) {
-      int owner = -1;
-      for (int q = 0; q < NN; ++q) {
-        const mmb_ir_node& Q = e->ir_nodes[q];
-        if (sampled(Q) && s >= Q.off && s < Q.off + Q.len) owner = q;
-      }
-      if (owner < 0) return fail(e, MMB_E_ARG, "node id %d reads value slot %d, which no sampled node owns", nid, s);
-      need[owner] = 1;
-    }
-  }
-  for (int q = 0; q < NN; ++q)
-    if (need[q] && colstart[q] < 0)
-      return fail(e, MMB_E_ARG, "node id %d is not monitored: the requested nodes need its draws", q);
-  for (int q = 0; q < NN; ++q) {
-    if (!need[q]) continue;
-    const mmb_ir_node& Q = e->ir_nodes[q];
-    for (int i = 0; i < Q.len; ++i) {
-      pl.col.push_back(colstart[q] + i);
-      pl.slot.push_back(Q.off + i);
-    }
-  }
-  return 0;
-}
-
-// lp of the n x K rows of `draws` into d_lp ([n][K], device), rows [r0, r0 + rows)
-static hipError_t ms_launch(mmb_engine* e, const SweepArgs& A, const MsPlan& pl, const int32_t* d_col,
-                            const int32_t* d_slot, int64_t rows, int K, const double* draws, int nnodes,
-                            const int32_t* nodes, double* d_lp) {
-  return mmb_launch_modelstats(e->model, A, e->P, e->ir_stack, rows, K, e->pmon, draws, nnodes, nodes, d_col, d_slot,
-                               (int)pl.col.size(), d_lp, e->stream);
-}
-
-// rows of the device lp scratch per pass: the n x K values are formed (and, for the deviance, reduced) in
-// chunks of at most this many doubles
-constexpr int64_t MS_CHUNK = 8ll << 20;
-
-// shared body: out_lp (host, Chains order out[i + n*k]) and / or acc (host, K x 2 deviance sums with `shift`)
-static int ms_run(mmb_engine* e, const char* what, int nnodes, const int32_t* nodes, int64_t n, int K,
-                  const double* draws, double* out_lp, double shift, double* acc) {
-  MsPlan pl;
-  if (int rc = ms_plan(e, nnodes, nodes, true, pl)) return rc;
-  HIPCHK(e, hipSetDevice(e->device));
-  SweepArgs A;
-  fill_args(e, A);
-  const int64_t crows = std::max<int64_t>(1, std::min<int64_t>(n, MS_CHUNK / K));
-  int32_t* d_tab = nullptr;
-  double *d_lp = nullptr, *d_acc = nullptr;
-  const size_t nc = pl.col.size();
-  hipError_t st = hipSuccess;
-  if (nc) {
-    st = hipMalloc(&d_tab, 2 * nc * sizeof(int32_t));
-    if (st == hipSuccess)
-      st = hipMemcpyAsync(d_tab, pl.col.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess)
-      st = hipMemcpyAsync(d_tab + nc, pl.slot.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-  }
-  if (st == hipSuccess) st = hipMalloc(&d_lp, (size_t)crows * K * sizeof(double));
-  if (st == hipSuccess && acc) {
-    st = hipMalloc(&d_acc, (size_t)2 * K * sizeof(double));
-    if (st == hipSuccess) st = hipMemsetAsync(d_acc, 0, (size_t)2 * K * sizeof(double), e->stream);
-  }
-  std::vector<double> h;
-  if (out_lp) h.resize((size_t)crows * K);
-  for (int64_t r0 = 0; r0 < n && st == hipSuccess; r0 += crows) {
-    const int64_t rows = std::min(crows, n - r0);
-    st = ms_launch(e, A, pl, d_tab, d_tab ? d_tab + nc : nullptr, rows, K,
-                   draws + (size_t)r0 * e->pmon * K, nnodes, nodes, d_lp);
-    if (st == hipSuccess && acc) st = mmb_launch_deviance(rows, K, d_lp, shift, d_acc, e->stream);
-    if (st == hipSuccess && out_lp) {
-      st = hipMemcpyAsync(h.data(), d_lp, (size_t)rows * K * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-      if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-      if (st == hipSuccess)
-        for (int64_t i = 0; i < rows; ++i)
-          for (int64_t k = 0; k < K; ++k) out_lp[(r0 + i) + n * k] = h[(size_t)i * K + k];
-    }
-  }
-  if (st == hipSuccess && acc)
-    st = hipMemcpyAsync(acc, d_acc, (size_t)2 * K * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  if (d_tab) (void)hipFree(d_tab);
-  if (d_lp) (void)hipFree(d_lp);
-  if (d_acc) (void)hipFree(d_acc);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "%s: %s", what, hipGetErrorString(st));
-  return 0;
-}
-
-int mmb_draws_logpdf(mmb_engine* e, int nnodes, const int32_t* nodes, double* out) {
-  if (!e || !nodes || !out) return fail(e, MMB_E_ARG, "null argument");
-  return ms_run(e, "draws_logpdf", nnodes, nodes, e->n_kept, (int)e->K, e->d_draws, out, 0.0, nullptr);
-}
-
-int mmb_draws_deviance(mmb_engine* e, int nnodes, const int32_t* nodes, double shift, double* out) {
-  if (!e || !nodes || !out) return fail(e, MMB_E_ARG, "null argument");
-  return ms_run(e, "draws_deviance", nnodes, nodes, e->n_kept, (int)e->K, e->d_draws, nullptr, shift, out);
-}
-
-int mmb_logpdf_at(mmb_engine* e, int nnodes, const int32_t* nodes, const double* x, double* lp) {
-  if (!e || !nodes || !x || !lp) return fail(e, MMB_E_ARG, "null argument");
-  {  // validated before anything is allocated (ms_run validates again on the same arguments)
-    MsPlan pl;
-    if (int rc = ms_plan(e, nnodes, nodes, true, pl)) return rc;
-  }
-  HIPCHK(e, hipSetDevice(e->device));
-  double* d_x = nullptr;  // a one-row, one-chain draw buffer
-  HIPCHK(e, hipMalloc(&d_x, (size_t)e->pmon * sizeof(double)));
-  hipError_t st = hipMemcpyAsync(d_x, x, (size_t)e->pmon * sizeof(double), hipMemcpyHostToDevice, e->stream);
-  int rc = 0;
-  if (st != hipSuccess) rc = fail(e, MMB_E_HIP, "logpdf_at: %s", hipGetErrorString(st));
-  else rc = ms_run(e, "logpdf_at", nnodes, nodes, 1, 1, d_x, lp, 0.0, nullptr);
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(d_x);
-  return rc;
-}
-
-// ---------------------------------------------------------------- posterior prediction (modelstats.jl:71-102)
-// The plan of a predict call: the node list's plan (ms_plan), the first result column of every list
-// entry and the result width P.  Everything is validated here, before any launch.
-struct PrPlan {
-  MsPlan ms;
-  std::vector<int32_t> col0;
-  int P = 0;
-};
-
-static int pr_plan(mmb_engine* e, int nnodes, const int32_t* nodes, PrPlan& pl) {
-  if (int rc = ms_plan(e, nnodes, nodes, true, pl.ms, "predict")) return rc;
-  if (e->model == MMB_MODEL_LINE) {
-    if (nnodes != 1 || nodes[0] != MMB_LINE_Y)
-      return fail(e, MMB_E_ARG, "predict: y (MMB_LINE_Y) is the only observed node of the line model");
-    pl.col0.assign(1, 0);
-    pl.P = 5;
-    return 0;
-  }
-  int64_t P = 0;
-  for (int a = 0; a < nnodes; ++a) {
-    const mmb_ir_node& N = e->ir_nodes[nodes[a]];
-    if (!N.fixed) return fail(e, MMB_E_ARG, "node id %d is not an observed Stochastic node of the model", nodes[a]);
-    if (N.family == MMB_IR_CATEGORICAL || N.family == MMB_IR_DISCRETEUNIFORM || N.family == MMB_IR_DIRICHLET)
-      return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d: Categorical, DiscreteUniform and Dirichlet variates are "
-                  "not lowered", nodes[a]);
-    const bool gam = N.family == MMB_IR_GAMMA || N.family == MMB_IR_INVGAMMA || N.family == MMB_IR_BETA;
-    if (gam && !mmb_pr_gblock_ok(nodes[a], N.len))
-      return fail(e, MMB_E_UNSUPPORTED, "predict: node id %d (length %d) does not fit the element blocks of the "
-                  "gamma streams (node id < 4095, 2 * length <= 65536)", nodes[a], N.len);
-    pl.col0.push_back((int32_t)P);
-    P += N.len;
-  }
-  int S, RS;
-  if (P > MMB_IR_MAX_VALUES * 4 || mmb_predict_tile(e->P, e->ir_stack, (int)P, &S, &RS) == 0)
-    return fail(e, MMB_E_UNSUPPORTED, "predict: a tile of 8 chains (%d state values and %lld predicted values each) "
-                "does not fit the 64 KiB of LDS: predict fewer nodes per call", e->P, (long long)P);
-  pl.P = (int)P;
-  return 0;
-}
-
-// doubles of the device scratch of predicted values per pass; MMB_PREDICT_CHUNK_ROWS (tests) caps its rows
-constexpr int64_t PR_CHUNK = 8ll << 20;
-
-// shared body over the kept rows [i0, i1): out (host, Chains order, (i1 - i0) x P x K) and / or acc (host,
-// K x P x 2 sums about `shift`, P values)
-static int pr_run(mmb_engine* e, const char* what, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start,
-                  int64_t thin, int64_t i0, int64_t i1, double* out, const double* shift, double* acc) {
-  PrPlan pl;
-  if (int rc = pr_plan(e, nnodes, nodes, pl)) return rc;
-  if (thin < 1 || start < 0) return fail(e, MMB_E_ARG, "%s: thin >= 1 and start >= 0", what);
-  if (i0 < 0 || i1 <= i0 || i1 > e->n_kept)
-    return fail(e, MMB_E_ARG, "window [%lld, %lld) is not inside the %lld kept draws", (long long)i0, (long long)i1,
-                (long long)e->n_kept);
-  HIPCHK(e, hipSetDevice(e->device));
-  SweepArgs A;
-  fill_args(e, A);
-  const int K = (int)e->K, P = pl.P;
-  const int64_t nw = i1 - i0;
-  int64_t crows = std::max<int64_t>(1, std::min<int64_t>(nw, PR_CHUNK / ((int64_t)P * K)));
-  if (const char* s = std::getenv("MMB_PREDICT_CHUNK_ROWS")) crows = std::max<int64_t>(1, std::min<int64_t>(crows, std::atoll(s)));
-  int32_t* d_tab = nullptr;
-  double *d_y = nullptr, *d_acc = nullptr, *d_shift = nullptr;
-  const size_t nc = pl.ms.col.size();
-  const size_t nacc = (size_t)2 * K * P;
-  hipError_t st = hipSuccess;
-  if (nc) {
-    st = hipMalloc(&d_tab, 2 * nc * sizeof(int32_t));
-    if (st == hipSuccess)
-      st = hipMemcpyAsync(d_tab, pl.ms.col.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess)
-      st = hipMemcpyAsync(d_tab + nc, pl.ms.slot.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-  }
-  if (st == hipSuccess) st = hipMalloc(&d_y, (size_t)crows * P * K * sizeof(double));
-  if (st == hipSuccess && acc) {
-    st = hipMalloc(&d_acc, nacc * sizeof(double));
-    if (st == hipSuccess) st = hipMemsetAsync(d_acc, 0, nacc * sizeof(double), e->stream);
-    if (st == hipSuccess) st = hipMalloc(&d_shift, (size_t)P * sizeof(double));
-    if (st == hipSuccess) st = hipMemcpyAsync(d_shift, shift, (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream);
-  }
-  std::vector<double> h;
-  if (out) h.resize((size_t)crows * P * K);
-  for (int64_t r0 = i0; r0 < i1 && st == hipSuccess; r0 += crows) {
-    const int64_t rows = std::min(crows, i1 - r0);
-    st = mmb_launch_predict(e->model, A, e->P, e->ir_stack, rows, K, e->pmon, e->d_draws + (size_t)r0 * e->pmon * K,
-                            nnodes, nodes, pl.col0.data(), P, d_tab, d_tab ? d_tab + nc : nullptr, (int)nc, seed,
-                            start + r0 * thin, thin, d_y, e->stream);
-    if (st == hipSuccess && acc) st = mmb_launch_predict_moments(rows, K, P, d_y, d_shift, d_acc, e->stream);
-    if (st == hipSuccess && out) {
-      st = hipMemcpyAsync(h.data(), d_y, (size_t)rows * P * K * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-      if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-      if (st == hipSuccess)
-        for (int64_t i = 0; i < rows; ++i)
-          for (int64_t j = 0; j < P; ++j)
-            for (int64_t k = 0; k < K; ++k) out[(r0 - i0 + i) + nw * (j + (int64_t)P * k)] = h[((size_t)i * P + j) * K + k];
-    }
-  }
-  if (st == hipSuccess && acc) st = hipMemcpyAsync(acc, d_acc, nacc * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-  const hipError_t sy = hipStreamSynchronize(e->stream);  // also after a failure: nothing is freed under a kernel
-  if (st == hipSuccess) st = sy;
-  if (d_tab) (void)hipFree(d_tab);
-  if (d_y) (void)hipFree(d_y);
-  if (d_acc) (void)hipFree(d_acc);
-  if (d_shift) (void)hipFree(d_shift);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "%s: %s", what, hipGetErrorString(st));
-  return 0;
-}
-
-int mmb_predict_width(mmb_engine* e, int nnodes, const int32_t* nodes, int64_t* P) {
-  if (!e || !nodes || !P) return fail(e, MMB_E_ARG, "null argument");
-  PrPlan pl;
-  if (int rc = pr_plan(e, nnodes, nodes, pl)) return rc;
-  *P = pl.P;
-  return 0;
-}
-
-int mmb_draws_predict(mmb_engine* e, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start, int64_t thin,
-                      int64_t i0, int64_t i1, double* out) {
-  if (!e || !nodes || !out) return fail(e, MMB_E_ARG, "null argument");
-  return pr_run(e, "draws_predict", nnodes, nodes, seed, start, thin, i0, i1, out, nullptr, nullptr);
-}
-
-int mmb_draws_predict_moments(mmb_engine* e, int nnodes, const int32_t* nodes, uint64_t seed, int64_t start,
-                              int64_t thin, const double* shift, double* out) {
-  if (!e || !nodes || !shift || !out) return fail(e, MMB_E_ARG, "null argument");
-  return pr_run(e, "draws_predict_moments", nnodes, nodes, seed, start, thin, 0, e->n_kept, nullptr, shift, out);
-}
-
-// ---------------------------------------------------------------- per-chain diagnostics
-static int diag_window(mmb_engine* e, int64_t i0, int64_t i1) {
-  if (i0 < 0 || i1 <= i0 || i1 > e->n_kept)
-    return fail(e, MMB_E_ARG, "window [%lld, %lld) is not inside the %lld kept draws", (long long)i0, (long long)i1,
-                (long long)e->n_kept);
-  return 0;
-}
-
-// launch (on the engine's stream) into a device buffer of `nout` doubles, copy back, free
-template <class Launch>
-static int diag_run(mmb_engine* e, const char* what, size_t nout, double* out, Launch launch) {
-  HIPCHK(e, hipSetDevice(e->device));
-  double* dout = nullptr;
-  HIPCHK(e, hipMalloc(&dout, nout * sizeof(double)));
-  hipError_t st = launch(dout);
-  if (st == hipSuccess) st = hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  (void)hipFree(dout);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "%s: %s", what, hipGetErrorString(st));
-  return 0;
-}
-
-int mmb_chain_autocov(mmb_engine* e, int64_t i0, int64_t i1, int nlags, const int64_t* lags, double* out) {
-  if (!e || !out || (nlags > 0 && !lags)) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  if (int rc = diag_window(e, i0, i1)) return rc;
-  if (nlags < 0 || nlags > MMB_DIAG_MAX_LAGS) return fail(e, MMB_E_ARG, "0 <= nlags <= %d", MMB_DIAG_MAX_LAGS);
-  for (int q = 0; q < nlags; ++q)
-    if (lags[q] < 1 || lags[q] >= i1 - i0)
-      return fail(e, MMB_E_ARG, "lags must be less than the sample length (lag %lld, window of %lld)",
-                  (long long)lags[q], (long long)(i1 - i0));
-  const int p = e->pmon;
-  return diag_run(e, "chain_autocov", (size_t)e->K * p * (2 + nlags), out, [&](double* dout) {
-    return mmb_launch_chain_autocov(p, (int)e->K, i0, i1, nlags, lags, e->d_draws, dout, e->stream);
-  });
-}
-
-// the window and method checks of mmb_chain_mcse
-static int mcse_window(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size) {
-  if (int rc = diag_window(e, i0, i1)) return rc;
-  const int64_t nw = i1 - i0;
-  if (etype == MMB_MCSE_BM) {
-    if (batch_size < 1) return fail(e, MMB_E_ARG, "batch size must be positive");
-    if (nw / batch_size < 2)   // mcse.jl:13-16
-      return fail(e, MMB_E_ARG, "iterations are < %lld and batch size is > %lld", (long long)(2 * batch_size),
-                  (long long)(nw / 2));
-  } else if (etype == MMB_MCSE_IMSE || etype == MMB_MCSE_IPSE) {
-    if (nw < 2) return fail(e, MMB_E_ARG, "lags must be less than the sample length (lag 1, window of 1)");
-  } else {
-    return fail(e, MMB_E_ARG, "unsupported mcse method %d", etype);
-  }
-  return 0;
-}
-
-int mmb_chain_mcse(mmb_engine* e, int64_t i0, int64_t i1, int etype, int64_t batch_size, double* out) {
-  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  if (int rc = mcse_window(e, i0, i1, etype, batch_size)) return rc;
-  const int p = e->pmon;
-  return diag_run(e, "chain_mcse", (size_t)e->K * p * MMB_MCSE_FIELDS, out, [&](double* dout) {
-    return mmb_launch_chain_mcse(p, (int)e->K, i0, i1, etype, batch_size, e->d_draws, dout, e->stream);
-  });
-}
-
-// heideldiag.jl:11-16 on every candidate window at once
-int mmb_chain_cvm(mmb_engine* e, int nstarts, const int64_t* starts, double* out) {
-  if (!e || !out || !starts) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  if (nstarts < 1 || nstarts > MMB_HEIDEL_MAX_STARTS)
-    return fail(e, MMB_E_ARG, "1 <= nstarts <= %d", MMB_HEIDEL_MAX_STARTS);
-  for (int q = 0; q < nstarts; ++q) {
-    if (starts[q] < 0 || starts[q] >= e->n_kept)
-      return fail(e, MMB_E_ARG, "start %lld is not inside the %lld kept draws", (long long)starts[q],
-                  (long long)e->n_kept);
-    if (q > 0 && starts[q] <= starts[q - 1]) return fail(e, MMB_E_ARG, "starts must be strictly increasing");
-  }
-  const int p = e->pmon;
-  return diag_run(e, "chain_cvm", (size_t)e->K * p * nstarts * 2, out, [&](double* dout) {
-    return mmb_launch_chain_cvm(p, (int)e->K, e->n_kept, nstarts, starts, e->d_draws, dout, e->stream);
-  });
-}
-
-// heideldiag.jl:24: mcse of each series' own window
-int mmb_chain_mcse_from(mmb_engine* e, const int64_t* i0, int64_t i1, int etype, int64_t batch_size, double* out) {
-  if (!e || !out || !i0) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  const int p = e->pmon;
-  const size_t nel = (size_t)e->K * p;
-  for (size_t q = 0; q < nel; ++q)
-    if (int rc = mcse_window(e, i0[q], i1, etype, batch_size)) {
-      const std::string why = e->err;
-      return fail(e, rc, "%s (chain %lld, param %d)", why.c_str(), (long long)(q / p), (int)(q % p));
-    }
-  HIPCHK(e, hipSetDevice(e->device));
-  int64_t* di = nullptr;
-  HIPCHK(e, hipMalloc(&di, nel * sizeof(int64_t)));
-  hipError_t st = hipMemcpyAsync(di, i0, nel * sizeof(int64_t), hipMemcpyHostToDevice, e->stream);
-  int rc = 0;
-  if (st != hipSuccess) rc = fail(e, MMB_E_HIP, "chain_mcse_from: %s", hipGetErrorString(st));
-  else
-    rc = diag_run(e, "chain_mcse_from", nel * MMB_MCSE_FIELDS, out, [&](double* dout) {
-      return mmb_launch_chain_mcse_from(p, (int)e->K, di, i1, etype, batch_size, e->d_draws, dout, e->stream);
-    });
-  (void)hipFree(di);
-  return rc;
-}
-
-// rafterydiag.jl:13-34; the quantile index is Julia 0.5 quantile's, split here
-int mmb_chain_raftery(mmb_engine* e, double q, double* out) {
-  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  if (!(q > 0.0 && q < 1.0)) return fail(e, MMB_E_ARG, "q is not in (0, 1)");
-  const int64_t n = e->n_kept;
-  if (n < 3 || n > 0x7fffffffll)
-    return fail(e, MMB_E_ARG, "the Raftery-Lewis counts need 3 <= kept draws < 2^31, got %lld", (long long)n);
-  const double index = 1.0 + (double)(n - 1) * q;
-  const double lo = floor(index);
-  const double h = index - lo;
-  const int interp = index != lo;
-  const int64_t rlo = (int64_t)lo - 1;
-  if (rlo < 0 || rlo + interp >= n) return fail(e, MMB_E_ARG, "quantile index %g outside 1 .. %lld", index, (long long)n);
-  const int p = e->pmon;
-  return diag_run(e, "chain_raftery", (size_t)e->K * p * MMB_RAFTERY_FIELDS, out, [&](double* dout) {
-    return mmb_launch_chain_raftery(p, (int)e->K, n, rlo, interp, h, e->d_draws, dout, e->stream);
-  });
-}
-
-int mmb_change_counts(mmb_engine* e, int64_t* out) {
-  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  if (e->n_kept < 1) return fail(e, MMB_E_STATE, "no device-kept draws (run with keep_device=1)");
-  HIPCHK(e, hipSetDevice(e->device));
-  const size_t nb = (size_t)(e->pmon + 1) * sizeof(unsigned long long);
-  unsigned long long* dc = nullptr;
-  HIPCHK(e, hipMalloc(&dc, nb));
-  hipError_t st = mmb_launch_change_counts(e->pmon, (int)e->K, e->n_kept, e->d_draws, dc, e->stream);
-  if (st == hipSuccess) st = hipMemcpyAsync(out, dc, nb, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  (void)hipFree(dc);
-  if (st != hipSuccess) return fail(e, MMB_E_HIP, "change_counts: %s", hipGetErrorString(st));
   return 0;
 }
 
@@ -3131,63 +1409,54 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
 }
 
 
+// the engine's counter words (d_nstat, zeros before mmb_init_chains): NUTS {updates, depth-cap hits,
+// depth sum}, [3] Slice overflows, [5] the AMWG count
+static int nstat_read(mmb_engine* e, unsigned long long (&v)[8]) {
+  std::memset(v, 0, sizeof v);
+  if (!e->d_nstat) return 0;
+  HIPCHK(e, hipSetDevice(e->device));
+  HIPCHK(e, hipMemcpyAsync(v, e->d_nstat, sizeof v, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 int mmb_nuts_stats(mmb_engine* e, int64_t* out) {
   if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  unsigned long long v[3] = {0, 0, 0};
-  if (e->d_nstat) {
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(v, e->d_nstat, sizeof v, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  }
+  unsigned long long v[8];
+  if (int rc = nstat_read(e, v)) return rc;
   for (int i = 0; i < 3; ++i) out[i] = (int64_t)v[i];
   return 0;
 }
 
 int mmb_amwg_stats(mmb_engine* e, int64_t* out) {
   if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (e->d_nstat) {
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(v, e->d_nstat, sizeof v, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  }
+  unsigned long long v[8];
+  if (int rc = nstat_read(e, v)) return rc;
   out[0] = (int64_t)v[5];
   return 0;
 }
 
-int mmb_amm_stats(mmb_engine* e, int64_t* out) {
+// out[b * width + i]: the first `width` words of block b's astat rows summed over the chains, for the
+// blocks of sampler `kind`
+static int astat_sums(mmb_engine* e, int kind, int width, int64_t* out) {
   if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  for (int i = 0; i < MMB_MAX_BLOCKS * MMB_AMM_STATS; ++i) out[i] = 0;
+  for (int i = 0; i < MMB_MAX_BLOCKS * width; ++i) out[i] = 0;
   if (e->K == 0) return 0;
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   std::vector<uint64_t> h;
   for (size_t b = 0; b < e->blocks.size(); ++b) {
-    if (!e->blocks[b].astat || e->blocks[b].spec.sampler != MMB_SAMPLER_AMM) continue;
+    if (!e->blocks[b].astat || e->blocks[b].spec.sampler != kind) continue;
     int rc = d2h(e, h, e->blocks[b].astat, (size_t)e->K * MMB_AMM_STAT_STRIDE);
     if (rc) return rc;
     for (int64_t k = 0; k < e->K; ++k)
-      for (int i = 0; i < MMB_AMM_STATS; ++i) out[b * MMB_AMM_STATS + i] += (int64_t)h[k * MMB_AMM_STAT_STRIDE + i];
+      for (int i = 0; i < width; ++i) out[b * width + i] += (int64_t)h[k * MMB_AMM_STAT_STRIDE + i];
   }
   return 0;
 }
 
-int mmb_rwm_stats(mmb_engine* e, int64_t* out) {
-  if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
-  for (int i = 0; i < MMB_MAX_BLOCKS * 2; ++i) out[i] = 0;
-  if (e->K == 0) return 0;
-  HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  std::vector<uint64_t> h;
-  for (size_t b = 0; b < e->blocks.size(); ++b) {
-    if (!e->blocks[b].astat || e->blocks[b].spec.sampler != MMB_SAMPLER_RWM) continue;
-    int rc = d2h(e, h, e->blocks[b].astat, (size_t)e->K * MMB_AMM_STAT_STRIDE);
-    if (rc) return rc;
-    for (int64_t k = 0; k < e->K; ++k)
-      for (int i = 0; i < 2; ++i) out[b * 2 + i] += (int64_t)h[k * MMB_AMM_STAT_STRIDE + i];
-  }
-  return 0;
-}
+int mmb_amm_stats(mmb_engine* e, int64_t* out) { return astat_sums(e, MMB_SAMPLER_AMM, MMB_AMM_STATS, out); }
+int mmb_rwm_stats(mmb_engine* e, int64_t* out) { return astat_sums(e, MMB_SAMPLER_RWM, 2, out); }
 
 int mmb_chain_order(mmb_engine* e, int32_t* slot_to_chain) {
   if (!e || !slot_to_chain) return fail(e, MMB_E_ARG, "null argument");
@@ -3211,27 +1480,27 @@ int mmb_debug_pchol(int device, int64_t n, int d, const double* S, double* L, in
   int dev0 = 0;
   hipError_t st = hipGetDevice(&dev0);
   if (st == hipSuccess) st = hipSetDevice(device);
-  hipStream_t ps = nullptr;
-  if (st == hipSuccess) st = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-  double *dS = nullptr, *dL = nullptr;
-  int32_t *dpos = nullptr, *dinfo = nullptr;
-  if (st == hipSuccess) st = hipMalloc(&dS, (size_t)n * TP * sizeof(double));
-  if (st == hipSuccess) st = hipMalloc(&dL, (size_t)n * TP * sizeof(double));
-  if (st == hipSuccess) st = hipMalloc(&dpos, (size_t)n * 32 * sizeof(int32_t));
-  if (st == hipSuccess) st = hipMalloc(&dinfo, (size_t)n * 2 * sizeof(int32_t));
-  if (st == hipSuccess) st = hipMemcpyAsync(dS, S, (size_t)n * TP * sizeof(double), hipMemcpyHostToDevice, ps);
-  if (st == hipSuccess) st = hipMemsetAsync(dL, 0, (size_t)n * TP * sizeof(double), ps);
-  if (st == hipSuccess) st = mmb_launch_pchol_probe((int)n, d, dS, dL, dpos, dinfo, ps);
-  if (st == hipSuccess) st = hipMemcpyAsync(L, dL, (size_t)n * TP * sizeof(double), hipMemcpyDeviceToHost, ps);
-  if (st == hipSuccess) st = hipMemcpyAsync(pos, dpos, (size_t)n * 32 * sizeof(int32_t), hipMemcpyDeviceToHost, ps);
-  if (st == hipSuccess) st = hipMemcpyAsync(info, dinfo, (size_t)n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ps);
-  if (st == hipSuccess) st = hipStreamSynchronize(ps);
-  if (ps) {
-    (void)hipStreamSynchronize(ps);  // (an error path: nothing in flight may use the buffers below)
-    (void)hipStreamDestroy(ps);
+  if (st == hipSuccess) {  // (the buffers go before the caller's device is restored)
+    DevBuf<double> dS, dL;
+    DevBuf<int32_t> dpos, dinfo;
+    hipStream_t ps = nullptr;
+    st = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
+    if (st == hipSuccess) st = dS.alloc((size_t)n * TP);
+    if (st == hipSuccess) st = dL.alloc((size_t)n * TP);
+    if (st == hipSuccess) st = dpos.alloc((size_t)n * 32);
+    if (st == hipSuccess) st = dinfo.alloc((size_t)n * 2);
+    if (st == hipSuccess) st = hipMemcpyAsync(dS, S, (size_t)n * TP * sizeof(double), hipMemcpyHostToDevice, ps);
+    if (st == hipSuccess) st = hipMemsetAsync(dL, 0, (size_t)n * TP * sizeof(double), ps);
+    if (st == hipSuccess) st = mmb_launch_pchol_probe((int)n, d, dS, dL, dpos, dinfo, ps);
+    if (st == hipSuccess) st = hipMemcpyAsync(L, dL, (size_t)n * TP * sizeof(double), hipMemcpyDeviceToHost, ps);
+    if (st == hipSuccess) st = hipMemcpyAsync(pos, dpos, (size_t)n * 32 * sizeof(int32_t), hipMemcpyDeviceToHost, ps);
+    if (st == hipSuccess) st = hipMemcpyAsync(info, dinfo, (size_t)n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ps);
+    if (st == hipSuccess) st = hipStreamSynchronize(ps);
+    if (ps) {
+      (void)hipStreamSynchronize(ps);  // (an error path: nothing in flight may use the buffers)
+      (void)hipStreamDestroy(ps);
+    }
   }
-  for (void* p : {(void*)dS, (void*)dL, (void*)dpos, (void*)dinfo})
-    if (p) (void)hipFree(p);
   (void)hipSetDevice(dev0);
   if (st != hipSuccess) return fail(nullptr, MMB_E_HIP, "mmb_debug_pchol: %s", hipGetErrorString(st));
   return 0;
@@ -3247,240 +1516,4 @@ int mmb_grad_evals(mmb_engine* e, int64_t* n) {
   HIPCHK(e, hipStreamSynchronize(e->stream));
   *n = (int64_t)v;
   return 0;
-}
-
-// ---------------------------------------------------------------- cross-GPU Gelman-Rubin (RCCL)
-// The one collective of the path (gelmandiag.jl:11-25): each local engine reduces
-// its kept draws to the mmb_gr_len sufficient statistics on device (gr.hip), then one SUM
-// all-reduce over RCCL/xGMI, in place in a per-engine device buffer; the global [min, max]
-// used for link() and the shift is one MAX all-reduce of (-min, max).
-// the agreement slot's value outside an agreement: flag 2 = "this rank could not stage" (comm_agree)
-static const double kAgreeFailed[4] = {2.0, 0.0, 0.0, 0.0};
-
-struct mmb_comm {
-  std::vector<mmb_engine*> eng;
-  std::vector<ncclComm_t> comm;
-  std::vector<double*> buf;  // per local engine: [L stats | 2p range | p shift | p link (int32) | 4 agree]
-  int p = 0;
-  int64_t L = 0;
-  double agree[4] = {0.0, 0.0, 0.0, 0.0};  // comm_agree's contribution (outlives its async H2D copies)
-};
-
-#define NCCLCHK(e, x)                                                                 \
-  do {                                                                                \
-    ncclResult_t r_ = (x);                                                            \
-    if (r_ != ncclSuccess) return fail((e), MMB_E_COMM, "%s: %s", #x, ncclGetErrorString(r_)); \
-  } while (0)
-
-__global__ void mmb_negate_mins(double* mm, int p) {
-  const int j = (int)threadIdx.x;
-  if (j < p) mm[2 * j] = -mm[2 * j];
-}
-
-int mmb_comm_id(uint8_t* id) {
-  if (!id) return fail(nullptr, MMB_E_ARG, "null argument");
-  ncclUniqueId u;
-  NCCLCHK(nullptr, ncclGetUniqueId(&u));
-  std::memcpy(id, u.internal, MMB_COMM_ID_BYTES);
-  return 0;
-}
-
-void mmb_comm_destroy(mmb_comm* c) {
-  if (!c) return;
-  for (size_t i = 0; i < c->eng.size(); ++i) {
-    (void)hipSetDevice(c->eng[i]->device);
-    if (c->comm[i]) (void)ncclCommDestroy(c->comm[i]);
-    if (c->buf[i]) (void)hipFree(c->buf[i]);
-  }
-  delete c;
-}
-
-int mmb_comm_init(mmb_engine** engines, int nlocal, int nranks, int rank0, const uint8_t* id, mmb_comm** out) {
-  if (!engines || !out || nlocal < 1) return fail(nullptr, MMB_E_ARG, "null argument or nlocal < 1");
-  *out = nullptr;
-  mmb_engine* e0 = engines[0];
-  if (!e0) return fail(nullptr, MMB_E_ARG, "null engine");
-  if (nranks < nlocal || rank0 < 0 || rank0 + nlocal > nranks)
-    return fail(e0, MMB_E_ARG, "ranks %d..%d outside 0..%d", rank0, rank0 + nlocal - 1, nranks - 1);
-  if (nlocal < nranks && !id) return fail(e0, MMB_E_ARG, "ranks span processes: pass the mmb_comm_id bytes of rank 0");
-  for (int i = 0; i < nlocal; ++i) {
-    if (!engines[i]) return fail(e0, MMB_E_ARG, "null engine %d", i);
-    if (engines[i]->pmon != e0->pmon) return fail(e0, MMB_E_ARG, "engines monitor different parameter counts");
-    for (int k = 0; k < i; ++k)
-      if (engines[k]->device == engines[i]->device) return fail(e0, MMB_E_ARG, "two local engines on device %d", engines[i]->device);
-  }
-  mmb_comm* c = new mmb_comm;
-  c->eng.assign(engines, engines + nlocal);
-  c->comm.assign(nlocal, nullptr);
-  c->buf.assign(nlocal, nullptr);
-  c->p = e0->pmon;
-  c->L = mmb_gr_len(e0);
-  const size_t nbuf = (size_t)c->L + 4 * (size_t)c->p + 4;
-  for (int i = 0; i < nlocal; ++i) {
-    // the agreement slot starts (and is left after every agreement) holding the failure flag, so
-    // a rank that cannot stage its contribution still contributes "failed" (comm_agree)
-    if (hipSetDevice(engines[i]->device) != hipSuccess || hipMalloc(&c->buf[i], nbuf * sizeof(double)) != hipSuccess ||
-        hipMemcpy(c->buf[i] + (nbuf - 4), kAgreeFailed, sizeof kAgreeFailed, hipMemcpyHostToDevice) != hipSuccess) {
-      mmb_comm_destroy(c);
-      return fail(e0, MMB_E_HIP, "comm buffer allocation failed");
-    }
-  }
-  ncclResult_t r;
-  if (nlocal == nranks && !id) {
-    std::vector<int> devs(nlocal);
-    for (int i = 0; i < nlocal; ++i) devs[i] = engines[i]->device;
-    r = ncclCommInitAll(c->comm.data(), nlocal, devs.data());
-  } else {
-    ncclUniqueId u;
-    std::memcpy(u.internal, id, MMB_COMM_ID_BYTES);
-    r = ncclGroupStart();
-    for (int i = 0; r == ncclSuccess && i < nlocal; ++i) {
-      (void)hipSetDevice(engines[i]->device);
-      r = ncclCommInitRank(&c->comm[i], nranks, u, rank0 + i);
-    }
-    ncclResult_t r2 = ncclGroupEnd();
-    if (r == ncclSuccess) r = r2;
-  }
-  if (r != ncclSuccess) {
-    mmb_comm_destroy(c);
-    return fail(e0, MMB_E_COMM, "RCCL communicator init (%d local of %d ranks): %s", nlocal, nranks,
-                ncclGetErrorString(r));
-  }
-  *out = c;
-  return 0;
-}
-
-static int comm_sync(mmb_comm* c) {
-  for (mmb_engine* e : c->eng) {
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  }
-  return 0;
-}
-
-// One in-place all-reduce of n doubles at offset off of every local engine's buffer, grouped.
-// ncclGroupEnd is called whatever happens inside the group, so a failed call never leaves the
-// thread's RCCL group open for later collectives.
-static ncclResult_t grouped_allreduce(mmb_comm* c, size_t off, size_t n, ncclRedOp_t op) {
-  ncclResult_t r = ncclGroupStart();
-  if (r != ncclSuccess) return r;
-  for (size_t i = 0; r == ncclSuccess && i < c->eng.size(); ++i)
-    r = ncclAllReduce(c->buf[i] + off, c->buf[i] + off, n, ncclDouble, op, c->comm[i], c->eng[i]->stream);
-  const ncclResult_t r2 = ncclGroupEnd();
-  return r != ncclSuccess ? r : r2;
-}
-
-// Agreement step before a data collective.  Every local engine contributes (flag, -n_kept,
-// n_kept) to one MAX all-reduce, where flag = 1 if this process cannot take part (too few kept
-// draws on some local engine) and 2 if it could not even stage its contribution: the slot holds
-// 2 outside an agreement (set at comm init and re-armed after every readback), so an engine whose
-// staging copy fails contributes the failure flag, never a stale "agree" of an earlier call.  A process whose precondition fails therefore still enters the
-// collective, and every rank sees the same verdict: all fail together (MMB_E_STATE for too few
-// draws, MMB_E_ARG when the ranks kept different numbers of draws, which would otherwise give
-// a silently wrong PSRF) or all proceed with the common n_kept.
-// A local HIP failure while staging the contribution does not skip the collective (the peers
-// are already waiting in it): the process always joins the all-reduce and the sync, and reports
-// its error afterwards (as mmb_gr_allreduce does for launch failures).
-static int comm_agree(mmb_comm* c, int64_t need, int64_t* nkept) {
-  mmb_engine* e0 = c->eng[0];
-  const size_t off = (size_t)c->L + 4 * (size_t)c->p;
-  int64_t lo = INT64_MAX, hi = -1;
-  for (mmb_engine* e : c->eng) { lo = std::min(lo, e->n_kept); hi = std::max(hi, e->n_kept); }
-  c->agree[0] = lo < need ? 1.0 : 0.0;
-  c->agree[1] = -(double)lo;
-  c->agree[2] = (double)hi;
-  c->agree[3] = 0.0;
-  int lrc = 0;
-  // MMB_TEST_COMM_STAGE_FAIL=1 (tests only): skip the staging copy as if it had failed
-  const char* tf = std::getenv("MMB_TEST_COMM_STAGE_FAIL");
-  const bool inject = tf && std::atoi(tf) == 1;
-  for (size_t i = 0; i < c->eng.size(); ++i) {
-    hipError_t st = hipSetDevice(c->eng[i]->device);
-    if (st == hipSuccess && inject) st = hipErrorUnknown;
-    if (st == hipSuccess)
-      st = hipMemcpyAsync(c->buf[i] + off, c->agree, sizeof(c->agree), hipMemcpyHostToDevice, c->eng[i]->stream);
-    if (st != hipSuccess && !lrc) lrc = fail(e0, MMB_E_HIP, "agreement staging: %s", hipGetErrorString(st));
-  }
-  const ncclResult_t r = grouped_allreduce(c, off, 4, ncclMax);
-  double all[4] = {2.0, 0.0, 0.0, 0.0};
-  hipError_t st = hipSetDevice(e0->device);
-  if (st == hipSuccess) st = hipMemcpyAsync(all, c->buf[0] + off, sizeof(all), hipMemcpyDeviceToHost, e0->stream);
-  for (size_t i = 0; i < c->eng.size(); ++i)  // re-arm: the slot holds the failure flag again
-    if (hipSetDevice(c->eng[i]->device) == hipSuccess)
-      (void)hipMemcpyAsync(c->buf[i] + off, kAgreeFailed, sizeof kAgreeFailed, hipMemcpyHostToDevice, c->eng[i]->stream);
-  const int rc = comm_sync(c);
-  if (r != ncclSuccess) return fail(e0, MMB_E_COMM, "agreement all-reduce: %s", ncclGetErrorString(r));
-  if (lrc)
-    return fail(e0, MMB_E_HIP, "%s (the agreement all-reduce saw flag %.0f: every rank fails this collective)",
-                g_last_error.c_str(), all[0]);
-  if (st != hipSuccess) return fail(e0, MMB_E_HIP, "agreement readback: %s", hipGetErrorString(st));
-  if (rc) return rc;
-  if (all[0] >= 2.0)
-    return fail(e0, MMB_E_COMM, "another rank could not stage its agreement contribution; collective skipped");
-  if (all[0] != 0.0)
-    return fail(e0, MMB_E_STATE, "need >= %lld device-kept draws per chain on every rank (this process: %lld)",
-                (long long)need, (long long)lo);
-  if (-all[1] != all[2])
-    return fail(e0, MMB_E_ARG, "ranks kept different numbers of draws (%.0f .. %.0f)", -all[1], all[2]);
-  *nkept = (int64_t)all[2];
-  return 0;
-}
-
-int mmb_range_allreduce(mmb_comm* c, double* minmax) {
-  if (!c || !minmax) return fail(nullptr, MMB_E_ARG, "null argument");
-  mmb_engine* e0 = c->eng[0];
-  const int p = c->p;
-  int64_t nk = 0;
-  int rc = comm_agree(c, 1, &nk);
-  if (rc) return rc;
-  for (size_t i = 0; i < c->eng.size(); ++i) {
-    mmb_engine* e = c->eng[i];
-    HIPCHK(e0, hipSetDevice(e->device));
-    double* mm = c->buf[i] + c->L;
-    hipError_t st = mmb_launch_gr_range(p, nk, (int)e->K, e->d_draws, mm, e->stream);
-    if (st == hipSuccess) {
-      hipLaunchKernelGGL(mmb_negate_mins, dim3(1), dim3(((p + 63) / 64) * 64), 0, e->stream, mm, p);
-      st = hipGetLastError();
-    }
-    // a local launch failure after the agreement still joins the all-reduce below (its peers
-    // are already committed to it); the error is reported afterwards
-    if (st != hipSuccess) rc = fail(e0, MMB_E_HIP, "gr_range: %s", hipGetErrorString(st));
-  }
-  const ncclResult_t r = grouped_allreduce(c, (size_t)c->L, 2 * (size_t)p, ncclMax);
-  if (r != ncclSuccess) return fail(e0, MMB_E_COMM, "range all-reduce: %s", ncclGetErrorString(r));
-  if (rc) return rc;
-  HIPCHK(e0, hipSetDevice(e0->device));
-  HIPCHK(e0, hipMemcpyAsync(minmax, c->buf[0] + c->L, 2 * p * sizeof(double), hipMemcpyDeviceToHost, e0->stream));
-  rc = comm_sync(c);
-  if (rc) return rc;
-  for (int j = 0; j < p; ++j) minmax[2 * j] = -minmax[2 * j];
-  return 0;
-}
-
-int mmb_gr_allreduce(mmb_comm* c, const int32_t* link, const double* shift, double* out) {
-  if (!c || !link || !shift || !out) return fail(nullptr, MMB_E_ARG, "null argument");
-  mmb_engine* e0 = c->eng[0];
-  const int p = c->p;
-  // every rank holds the same model, so all refuse alike before any collective
-  if (int wrc = gr_width_check(e0)) return wrc;
-  int64_t nk = 0;
-  int rc = comm_agree(c, 2, &nk);
-  if (rc) return rc;
-  for (size_t i = 0; i < c->eng.size(); ++i) {
-    mmb_engine* e = c->eng[i];
-    HIPCHK(e0, hipSetDevice(e->device));
-    double* ds = c->buf[i] + c->L + 2 * p;
-    int32_t* dl = (int32_t*)(ds + p);
-    hipError_t st = hipMemcpyAsync(ds, shift, p * sizeof(double), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess) st = hipMemcpyAsync(dl, link, p * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess) st = mmb_launch_gr_stats(p, nk, (int)e->K, e->d_draws, dl, ds, c->buf[i], e->stream);
-    if (st != hipSuccess) rc = fail(e0, MMB_E_HIP, "gr_stats: %s", hipGetErrorString(st));
-  }
-  const ncclResult_t r = grouped_allreduce(c, 0, (size_t)c->L, ncclSum);
-  if (r != ncclSuccess) return fail(e0, MMB_E_COMM, "Gelman-Rubin all-reduce: %s", ncclGetErrorString(r));
-  if (rc) { (void)comm_sync(c); return rc; }
-  HIPCHK(e0, hipSetDevice(e0->device));
-  HIPCHK(e0, hipMemcpyAsync(out, c->buf[0], c->L * sizeof(double), hipMemcpyDeviceToHost, e0->stream));
-  // the host copies of link/shift must outlive the async H2D copies: wait before returning
-  return comm_sync(c);
 }

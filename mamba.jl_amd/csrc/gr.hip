@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "mmb_math.h"
+#include "launch.h"
 
 #define GR_PMAX 4
 #define GR_THREADS 256
@@ -255,7 +256,7 @@ hipError_t mmb_launch_gr_range(int pmon, int64_t n, int K, const double* draws, 
   return e;
 }
 
-// the widest model the Gelman-Rubin sums serve (engine.cpp refuses wider ones by name)
+// the widest model the Gelman-Rubin sums serve (engine_post.cpp refuses wider ones by name)
 int mmb_gr_pmax() { return GR_BIG_PMAX; }
 
 hipError_t mmb_launch_gr_stats(int pmon, int64_t n, int K, const double* draws, const int32_t* link,

@@ -35,6 +35,7 @@
 #include <string.h>
 
 #include "order_key.h"
+#include "launch.h"
 
 #define HPD_THREADS 256
 #define HPD_ROWS 16                                 // rows a thread has in flight in the collect pass

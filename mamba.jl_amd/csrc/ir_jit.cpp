@@ -675,7 +675,7 @@ std::string mmb_ir_jit_source(const mmb_model_spec& spec, const mmb_ir_model& ir
   }
   if (kinds & (1u << MMB_SAMPLER_AMWG)) {
     // element terms and term weights of the AMWG blocks' logpdf! (lane-parallel decisions, ir.h
-    // amwg_dm; used only on blocks the engine finds separable, engine.cpp ir_sep_table)
+    // amwg_dm; used only on blocks the engine finds separable, engine_ir.cpp ir_sep_table)
     std::vector<char> en(ir.nnodes, 0);
     for (int b = 0; b < spec.nblocks; ++b)
       if (spec.blocks[b].sampler == MMB_SAMPLER_AMWG)

@@ -29,6 +29,7 @@
 // The engine uses this kernel for a line scheme that is one AMM block (any d <= 3, emap,
 // transform, sigl, adapt); MMB_LINE_GENERIC=1 selects the generic kernel.
 #include "samplers.h"
+#include "launch.h"
 
 #ifdef MMB_PHASE_PROF
 #include <cstdio>

@@ -15,6 +15,7 @@
 #include "hmc.h"
 #include "logistic.h"
 #include "nuts.h"
+#include "launch.h"
 
 typedef double mmb_d4 __attribute__((ext_vector_type(4)));
 

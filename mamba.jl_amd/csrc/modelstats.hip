@@ -30,6 +30,7 @@
 // ms_deviance_kernel: per chain, [sum_i (D - c), sum_i (D - c)^2] with D = -2 lp, in row order,
 //   continued over row chunks (the n x K values stay on the device; non-finite values propagate).
 #include "modelstats.h"
+#include "launch.h"
 
 #define MS_DEV_THREADS 64   // deviance reduction: one wavefront per workgroup spreads few chains over the CUs
 #define MS_DEV_ROWS 16      // its loads in flight per thread

@@ -31,6 +31,7 @@
 //   row order, continued over row chunks (ms_deviance_kernel's scheme; non-finite values propagate).
 #include "modelstats.h"
 #include "predict_math.h"
+#include "launch.h"
 
 #define PR_MOM_THREADS 64
 #define PR_MOM_ROWS 16  // loads in flight per thread

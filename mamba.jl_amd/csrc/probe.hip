@@ -5,6 +5,7 @@
 // the oracle's dpstf2 (oracle.c orc_pchol; amm.jl:87, LAPACK dpstf2 for n < 64) on inputs the
 // sampler rarely produces.  Diagnostics only (mmb_debug_pchol); not on the sampling path.
 #include "sweep.h"
+#include "launch.h"
 
 namespace {
 using PM = Mdl<MMB_MODEL_RATS>;

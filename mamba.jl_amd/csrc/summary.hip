@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "order_key.h"
+#include "launch.h"
 
 #define SS_THREADS 256
 #define SS_FIELDS 10

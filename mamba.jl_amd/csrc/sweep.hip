@@ -1,6 +1,7 @@
 // sweep.hip — the static instantiations of the block-sweep kernel (sweep.h) and their
 // host-side launchers (line, rats, the node-IR interpreter).
 #include "sweep.h"
+#include "launch.h"
 #include <cstdlib>
 
 #ifdef MMB_PHASE_PROF
@@ -151,8 +152,6 @@ hipError_t mmb_launch_order_chains(const OrderArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(order_chains_kernel, dim3(1), dim3(ORD_T), 0, st, a);
   return hipGetLastError();
 }
-
-hipError_t mmb_launch_line_amm(const SweepArgs& A, hipStream_t st);  // line_amm.hip
 
 // host-side launcher (engine.cpp); kinds = bitmask of the scheme's sampler kinds
 hipError_t mmb_launch_sweep(int model, unsigned kinds, const SweepArgs& A, hipStream_t st) {

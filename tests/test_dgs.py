@@ -38,7 +38,7 @@ def test_abi_constants(mamba):
         assert re.search(rf"\b{name} = {val}\b", hdr), name
     assert re.search(r"#define MMB_ABI_VERSION 10\b", hdr)
     assert re.search(r"#define MMB_DGS_MAX_SUPPORT 32\b", hdr)
-    # the fused device opcodes of the new leaves stay inside the opcode byte (engine.cpp ir_fuse)
+    # the fused device opcodes of the new leaves stay inside the opcode byte (engine_ir.cpp ir_fuse)
     assert 64 + 4 * (a.IR_OP["datav"] - 1) + 3 < 256
 
 

@@ -11,7 +11,10 @@
 * the lane-parallel AMWG decision (samplers.h amwg_lanes) with accept uniforms placed a few ulps
   to 2^-12 off each coordinate's threshold exp(d_j) (MMB_AMWG_PROBE=1, mmb_math.h
   mmb_amwg_probe_factor, kernels and oracle alike): both certain and uncertain decisions occur,
-  and every mode (default, MMB_AMWG_EXACT=1) equals the oracle bit for bit (amwg.jl:99-115)."""
+  and every mode (default, MMB_AMWG_EXACT=1) equals the oracle bit for bit (amwg.jl:99-115);
+* mmb_init_chains on an engine that already holds chains (engine.cpp free_dev drops the per-chain
+  buffers as one group): the re-initialised engine equals a fresh one bit for bit, on the line model
+  and on a node-IR model whose separable-AMWG table lives as long as the engine."""
 import numpy as np
 import pytest
 
@@ -197,6 +200,64 @@ def test_amm_crafted_moments_match_oracle(mamba, oracle):
             (so[b]["updates"], so[b]["full_rank"], so[b]["rank_sum"]), (b, sg[b], so[b])
         assert sg[b]["redo"] > 0, sg[b]
         assert 0 < sg[b]["full_rank"] < sg[b]["updates"]
+
+
+def _reinit_calls(eng, init, seed):
+    """init_chains, 20 iterations, the tune row read and written back, 10 more: what a fresh engine and a
+    re-initialised one are compared on."""
+    eng.init_chains(init, seed=seed)
+    d1 = eng.run(20, burnin=0, thin=1)
+    tune = eng.tune()
+    eng.set_tune(tune)
+    np.testing.assert_array_equal(eng.tune(), tune)  # get_tune round-trips
+    d2 = eng.run(10, burnin=0, thin=1)
+    return d1, d2, tune, eng.tune(), eng.values()
+
+
+def _assert_same_run(a, b):
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
+
+
+def test_reinit_live_engine_line(mamba):
+    """mmb_init_chains on an engine that already holds chains drops every per-chain buffer (the AMWG,
+    AMM and per-element Slice width arrays of the blocks among them) and allocates them for the new chain
+    count: a live engine re-initialised from K = 3 to K = 5 then equals a fresh K = 5 engine bit for bit."""
+    def model():
+        m = mamba.line()
+        m.setinputs(mamba.model.LINE_DATA)
+        return m.setsamplers([mamba.AMWG("s2", 1.0), mamba.AMM("beta", np.eye(2)),
+                              mamba.Slice(["beta", "s2"], [3.0, 1.0, 2.0], mamba.Univariate)])
+    init = mamba.model.line_init_matrix(5, seed=4)
+    live = mamba.Engine(model())
+    live.init_chains(init[:3], seed=3)
+    assert live.run(20, burnin=0, thin=1).shape == (20, 3, 3)
+    got = _reinit_calls(live, init, 9)
+    want = _reinit_calls(mamba.Engine(model()), init, 9)
+    assert got[0].shape == (20, 3, 5)
+    _assert_same_run(got, want)
+
+
+def test_reinit_live_engine_ir_separable(mamba):
+    """The same on a node-IR engine whose AMWG block separates by coordinate (seeds b): the block's
+    coordinate table is built at mmb_create_ir and must outlive the per-chain buffers."""
+    ir = mamba.ir
+
+    def example(K):  # seeds.jl:69-71, as tests/test_gpu_ir.py
+        m = ir.seeds_model().setinputs(ir.SEEDS)
+        m.setsamplers([mamba.AMM(["alpha0", "alpha1", "alpha2", "alpha12"], 0.01 * np.eye(4)),
+                       mamba.AMWG("b", 0.01), mamba.AMWG("s2", 0.1)])
+        return m, m.init_matrix([ir.seeds_inits()[k % 2] for k in range(K)], K)
+    m, V = example(256)
+    live = mamba.Engine(m)
+    assert "lane-parallel AMWG blocks: 1 of" in live.ir_jit()[1], live.ir_jit()
+    live.init_chains(V[:96], seed=3)
+    live.run(20, burnin=0, thin=1)
+    got = _reinit_calls(live, V, 23)
+    m2, V2 = example(256)
+    want = _reinit_calls(mamba.Engine(m2), V2, 23)
+    _assert_same_run(got, want)
+    assert got[4].shape[0] == 256
 
 
 def test_amwg_near_threshold_uniforms_match_oracle(mamba, oracle, monkeypatch):

@@ -115,7 +115,7 @@ def test_ir_gpu_vs_oracle(mamba, oracle, case, kernel, monkeypatch):
 
 @pytest.mark.parametrize("name", ["rats", "seeds", "blocker"])
 def test_ir_lane_parallel_amwg(mamba, oracle, name, monkeypatch):
-    """AMWG blocks whose logpdf! separates by coordinate (engine.cpp ir_sep_table: every element
+    """AMWG blocks whose logpdf! separates by coordinate (engine_ir.cpp ir_sep_table: every element
     term reads at most one coordinate -- rats alpha / beta through the y gather, seeds b, blocker
     delta) decide all coordinates at once in the specialised kernel (ir.h amwg_dm); the draws,
     values and tune equal the one-coordinate-at-a-time loop (MMB_IR_SEP=0), the band-widened mode

@@ -333,7 +333,7 @@ def test_rats_carried_proposal_resume_after_switch(mamba, oracle, tmp_path, how)
 
 
 def mamba_tune_lens(mamba, m):
-    """Canonical tune-row length of each block (engine.cpp mmb_get_tune layout)."""
+    """Canonical tune-row length of each block (engine_tune.cpp mmb_get_tune layout)."""
     out = []
     for s in m.samplers:
         d = m.block_dim(s)
@@ -771,7 +771,7 @@ def test_gr_allreduce_rccl_one_gpu(mamba, how):
 
 
 def test_gr_allreduce_agreement_fails_together(mamba):
-    """The collective's agreement step (engine.cpp comm_agree): a process whose engines hold
+    """The collective's agreement step (engine_comm.cpp comm_agree): a process whose engines hold
     too few kept draws fails with MMB_E_STATE *after* joining one MAX all-reduce (its peers
     do not block), and the RCCL group is closed afterwards: the next collectives on the
     same communicator still work."""
