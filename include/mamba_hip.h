@@ -89,9 +89,20 @@ typedef enum {
   MMB_SAMPLER_RWM = 8,   /* src/samplers/rwm.jl:49-71 (additive: the ABI version is unchanged) */
   MMB_SAMPLER_DGS = 9,   /* src/samplers/dgs.jl:56-126: discrete Gibbs sampling of one discrete node-IR node
                             (additive: the ABI version is unchanged) */
-  MMB_SAMPLER_SLICESIMPLEX = 10 /* src/samplers/slicesimplex.jl:24-122: slice sampling of one Dirichlet node-IR node
-                                   on its simplex; mmb_block_spec.scale in (0, 1], no tune state (additive too) */
+  MMB_SAMPLER_SLICESIMPLEX = 10, /* src/samplers/slicesimplex.jl:24-122: slice sampling of one Dirichlet node-IR node
+                                    on its simplex; mmb_block_spec.scale in (0, 1], no tune state (additive too) */
+  /* The binary samplers of one Bernoulli or DiscreteUniform(0, 1) node-IR node of 1..32 elements (additive too).
+   * BMG / BMC3: k is an int in mmb_block_spec.nsteps (form = MMB_BINARY_K_INT), or index lists in tuning, one
+   * 32-bit mask per list (bit i = element i + 1) stored as a double, 1..MMB_BINARY_MAX_LISTS of them
+   * (form = MMB_BINARY_K_LISTS); no tune state.  BIA: epsilon in epsilon, decay in beta, target in target,
+   * the initial A[dim] then D[dim] in tuning; tune row [iter, A[dim], D[dim]]. */
+  MMB_SAMPLER_BMG = 11,  /* src/samplers/bmg.jl:57-101: binary Metropolised Gibbs */
+  MMB_SAMPLER_BMC3 = 12, /* src/samplers/bmc3.jl:57-65: binary MC3 */
+  MMB_SAMPLER_BIA = 13   /* src/samplers/bia.jl:70-119: binary individual adaptation */
 } mmb_sampler_kind;
+typedef enum { MMB_BINARY_K_INT = 0, MMB_BINARY_K_LISTS = 1 } mmb_binary_form;
+#define MMB_BINARY_MAX_LISTS 64
+#define MMB_BINARY_MAX 32
 
 typedef enum { MMB_ADAPT_ALL = 0, MMB_ADAPT_BURNIN = 1, MMB_ADAPT_NONE = 2 } mmb_adapt;
 typedef enum { MMB_SLICE_MULTIVARIATE = 0, MMB_SLICE_UNIVARIATE = 1 } mmb_slice_form;
@@ -120,18 +131,20 @@ typedef struct {
   int32_t nnodes;                          /* number of nodes in `params` */
   int32_t nodes[MMB_MAX_NODES_PER_BLOCK];  /* node ids in block (params) order */
   int32_t adapt;                           /* AMWG/AMM: mmb_adapt (default :all) */
-  int32_t form;                            /* Slice: mmb_slice_form (default Multivariate); RWM: mmb_rwm_proposal */
+  int32_t form;                            /* Slice: mmb_slice_form (default Multivariate); RWM: mmb_rwm_proposal;
+                                              BMG/BMC3: mmb_binary_form */
   int32_t transform;                       /* Slice: transform flag (default false); AMWG/AMM/NUTS/RWM use true */
   int32_t batchsize;                       /* AMWG batchsize (default 50) */
-  double target;                           /* AMWG target (0.44) / NUTS target (0.6) */
-  double beta;                             /* AMM beta (0.05) */
+  double target;                           /* AMWG target (0.44) / NUTS target (0.6) / BIA target (0.45) */
+  double beta;                             /* AMM beta (0.05); BIA decay (0.55) */
   double scale;                            /* AMM scale (2.38); SliceSimplex scale in (0, 1] */
   int32_t dim;                             /* unlisted block length (checked by mmb_create) */
   int32_t ntuning;                         /* length of `tuning` */
   const double* tuning;                    /* AMWG sigma[dim] | Slice width[dim] | RWM scale[dim] | AMM Sigma[dim*dim] col-major
-                                              | HMC/MALA Sigma[dim*dim] col-major, or none (SigmaL = I) */
-  double epsilon;                          /* HMC/MALA step size (hmc.jl:13, mala.jl:12) */
-  int32_t nsteps;                          /* HMC leapfrog steps L (hmc.jl:13) */
+                                              | HMC/MALA Sigma[dim*dim] col-major, or none (SigmaL = I)
+                                              | BMG/BMC3 list masks | BIA A[dim], D[dim] */
+  double epsilon;                          /* HMC/MALA step size (hmc.jl:13, mala.jl:12); BIA epsilon (bia.jl:21) */
+  int32_t nsteps;                          /* HMC leapfrog steps L (hmc.jl:13); BMG/BMC3 int k */
   int32_t gradient;                        /* NUTS/HMC/MALA logpdfgrad! (sampler.jl:97-111): mmb_gradient */
 } mmb_block_spec;
 
@@ -182,8 +195,9 @@ typedef enum {
 #define MMB_SIMPLEX_TOL 1e-8
 #define MMB_SIMPLEX_MAX 32
 #define MMB_IR_CAT_STATE(off) (-2 - (off))
-/* A sampled discrete node (Bernoulli, Binomial, Categorical, DiscreteUniform) is updated by a DGS block only,
- * and a DGS block holds exactly one such node; its support is the integers lo..hi (Binomial: 0..n_i of
+/* A sampled discrete node (Bernoulli, Binomial, Categorical, DiscreteUniform) is updated by a DGS block, or, when
+ * it is binary (Bernoulli, DiscreteUniform(0, 1)) and has at most MMB_BINARY_MAX elements, by a BMG, BMC3 or BIA
+ * block; each such block holds exactly one such node.  Its support is the integers lo..hi (Binomial: 0..n_i of
  * element i), at most MMB_DGS_MAX_SUPPORT values.  Off the support its log density is -Inf. */
 #define MMB_DGS_MAX_SUPPORT 32
 
@@ -613,9 +627,11 @@ int mmb_amm_stats(mmb_engine* e, int64_t* out /* MMB_MAX_BLOCKS x MMB_AMM_STATS 
  * Both paths give the same draws; diagnostics only. */
 int mmb_amwg_stats(mmb_engine* e, int64_t* out /* 1 */);
 
-/* RWM counters since mmb_init_chains, per sampling block b (zero rows for non-RWM blocks), summed
+/* RWM counters since mmb_init_chains, per sampling block b (zero rows for the other blocks), summed
  * over the engine's chains: out[2 b] = block updates, out[2 b + 1] = accepted ones (rwm.jl:67-70).
- * A user sizes `scale` from this acceptance rate (RWM does not adapt).  Diagnostics only. */
+ * A user sizes `scale` from this acceptance rate (RWM does not adapt).  BMG, BMC3 and BIA blocks fill
+ * their rows the same way (a BMG block of one element has no accept step: every update counts as
+ * accepted).  Diagnostics only. */
 int mmb_rwm_stats(mmb_engine* e, int64_t* out /* MMB_MAX_BLOCKS x 2 */);
 
 /* The lane-group slot -> chain table the next window will run with (K entries; the identity

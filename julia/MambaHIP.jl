@@ -26,6 +26,8 @@ const MMB_MODEL_LINE, MMB_MODEL_RATS, MMB_MODEL_LOGISTIC = Int32(1), Int32(2), I
 const MMB_SAMPLER_AMWG, MMB_SAMPLER_AMM, MMB_SAMPLER_NUTS, MMB_SAMPLER_SLICE = Int32(1), Int32(2), Int32(3), Int32(4)
 const MMB_SAMPLER_GIBBS, MMB_SAMPLER_HMC, MMB_SAMPLER_MALA = Int32(5), Int32(6), Int32(7)
 const MMB_SAMPLER_RWM = Int32(8)
+# the binary samplers of node-IR models (bmg.jl, bmc3.jl, bia.jl): ids only, the shim does not register them yet
+const MMB_SAMPLER_BMG, MMB_SAMPLER_BMC3, MMB_SAMPLER_BIA = Int32(11), Int32(12), Int32(13)
 # mmb_rwm_proposal: Normal and the SymDistributionTypes (src/distributions/extensions.jl:51-53)
 const MMB_RWM_PROPOSAL = Dict{Any,Int32}(Distributions.Normal => 0, Mamba.SymUniform => 1,
                                          Mamba.SymTriangularDist => 2, Mamba.Epanechnikov => 3,

@@ -20,6 +20,10 @@ MMB_DGS_MAX_SUPPORT = 32
 MMB_SAMPLER_SLICESIMPLEX = 10  # additive too
 MMB_SIMPLEX_MAX, MMB_SIMPLEX_TOL = 32, 1e-8
 MMB_SUB_SIMPLEX = 6  # csrc/mmb_math.h: the Dirichlet(1, ..., 1) draws of a SliceSimplex block
+MMB_SAMPLER_BMG, MMB_SAMPLER_BMC3, MMB_SAMPLER_BIA = 11, 12, 13  # the binary samplers: additive too
+MMB_BINARY_K_INT, MMB_BINARY_K_LISTS = 0, 1  # mmb_block_spec.form of BMG / BMC3
+MMB_BINARY_MAX_LISTS, MMB_BINARY_MAX = 64, 32
+MMB_SUB_BINARY = 7  # csrc/mmb_math.h: index-set uniforms of BMG / BMC3, proposal uniforms of BIA
 (MMB_RWM_NORMAL, MMB_RWM_SYMUNIFORM, MMB_RWM_SYMTRIANGULAR, MMB_RWM_EPANECHNIKOV, MMB_RWM_BIWEIGHT,
  MMB_RWM_TRIWEIGHT, MMB_RWM_COSINE) = range(7)
 MMB_ABI_VERSION = 10

@@ -110,17 +110,19 @@ __device__ __forceinline__ bool mmb_rcp_seeded_doubt(double x) {
 
 // Per-block descriptor passed in kernel arguments (constant memory, uniform access).
 struct DBlock {
-  int32_t kind, nn, d, transform, form, adapt, batchsize, sigl_diag;
+  int32_t kind, nn, d, transform, form, adapt, batchsize, sigl_diag;  // batchsize: BMG / BMC3 the int k, or the
+                                                                        // number of index lists (form)
   int32_t nodes[4];
   int32_t emap[4];       // line/rats scalar blocks: element -> value index / node id
-  double target, beta, scale;
+  double target, beta, scale;  // BIA: target, decay, epsilon
   double width0;         // Slice: scalar width
-  const double* width;   // Slice: widths[d] (device) or null when scalar
+  const double* width;   // Slice: widths[d] (device) or null when scalar; BMG / BMC3 list form: one 32-bit element
+                         // mask per index list, stored as doubles
   const double* sigl;    // AMM, HMC/MALA: chol(Sigma) lower, row-major d x d (device); HMC/MALA: null = I
   // tune state (device, chain-major)
-  double* t_sigma;       // AMWG  [K][DP]; RWM [K][DP] scale (RWMTune.scale)
-  double* t_accept;      // AMWG  [K][DP]
-  int32_t* t_m;          // AMWG/AMM/NUTS m [K]
+  double* t_sigma;       // AMWG  [K][DP]; RWM [K][DP] scale (RWMTune.scale); BIA [K][DP] A (BIATune.A)
+  double* t_accept;      // AMWG  [K][DP]; BIA [K][DP] D (BIATune.D)
+  int32_t* t_m;          // AMWG/AMM/NUTS m [K]; BIA iter [K]
   int32_t* t_flags;      // [K] bit0 adapt, bit1 AMM alias, bit2 AMM factor valid, bit3 NUTS init,
                          //     bit4 AMM factor not stored yet (samplers.h amm: set and cleared within a launch)
   double* t_Mv;          // AMM   [K][DP]
@@ -134,7 +136,7 @@ struct DBlock {
                          //       with the factor still in registers), valid when t_xtag[c] matches
   int64_t* t_xtag;       // AMM   [K] (xepoch << 32) | iteration the carried proposal is for
   uint64_t* t_astat;     // AMM   [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats), diagnostics;
-                         // RWM   the same rows: [0] updates, [1] accepts (mmb_rwm_stats)
+                         // RWM, BMG, BMC3, BIA   the same rows: [0] updates, [1] accepts (mmb_rwm_stats)
   double* t_nuts;        // NUTS  [K][8] eps, epsbar, Hbar, mu, alpha, nalpha, -, -
   double* t_nfr;         // NUTS  [K][NutsFrames<DV>::DBL] tree frames (scratch, nuts.h)
   double* t_hmc;         // HMC/MALA [K][2] epsilon, L (HMCTune / MALATune, hmc.jl:5-28)

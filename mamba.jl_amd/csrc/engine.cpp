@@ -25,8 +25,9 @@ int node_dim(const mmb_model_spec& s, const mmb_ir_model* ir, int node, bool* po
   bool pos = false;
   int d = -1;
   if (s.model == MMB_MODEL_IR) {
-    // sampled nodes only: not fixed, not Logical; a discrete family only where a DGS block samples it,
-    // a Dirichlet node only where a SliceSimplex block does (ir_validate and create_impl check both)
+    // sampled nodes only: not fixed, not Logical; a discrete family only where a DGS block (or, a binary
+    // node, a BMG, BMC3 or BIA block) samples it, a Dirichlet node only where a SliceSimplex block does
+    // (ir_validate and create_impl check both)
     if (ir && node >= 0 && node < ir->nnodes) {
       const mmb_ir_node& n = ir->nodes[node];
       const bool ok = !n.fixed && ((n.family >= MMB_IR_NORMAL && n.family <= MMB_IR_BETA) || ir_dgs_family(n.family) ||
@@ -288,6 +289,73 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
         }
         e->ssx_kmax = std::max(e->ssx_kmax, d);
         break;
+      case MMB_SAMPLER_BMG:
+      case MMB_SAMPLER_BMC3:
+      case MMB_SAMPLER_BIA: {  // bmg.jl:26-37, bmc3.jl:26-37, bia.jl:36-50 (validate): one binary node per block
+        const char* nm = binary_name(s.sampler);
+        if (e->model != MMB_MODEL_IR) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: %s samples binary nodes of node-IR models only", b, nm);
+        }
+        if (s.nnodes != 1) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: a %s block holds exactly one node (one joint step over its "
+                      "elements)", b, nm);
+        }
+        if (!ir_binary_node(ir->nodes[s.nodes[0]])) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: %s samples a Bernoulli or DiscreteUniform(0, 1) node; node %d "
+                      "is not binary", b, nm, s.nodes[0]);
+        }
+        if (d < 1 || d > MMB_BINARY_MAX) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: a %s block holds a node of 1..%d elements", b, nm, MMB_BINARY_MAX);
+        }
+        const double all = d >= 32 ? 4294967295.0 : (double)((1u << d) - 1u);
+        if (s.sampler != MMB_SAMPLER_BIA && s.form == MMB_BINARY_K_INT) {
+          if (s.nsteps < 1 || s.nsteps > d) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: k exceeds variate length %d", b, d);
+          }
+        } else if (s.sampler != MMB_SAMPLER_BIA && s.form == MMB_BINARY_K_LISTS) {
+          if (s.ntuning < 1 || s.ntuning > MMB_BINARY_MAX_LISTS) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: k holds 1..%d index lists", b, MMB_BINARY_MAX_LISTS);
+          }
+          for (int i = 0; i < s.ntuning; ++i)
+            if (!(s.tuning[i] >= 1.0 && s.tuning[i] <= all && s.tuning[i] == std::floor(s.tuning[i]))) {
+              delete e;
+              return fail(nullptr, MMB_E_ARG, "block %d: indices in k exceed variate length %d", b, d);
+            }
+        } else if (s.sampler != MMB_SAMPLER_BIA) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: unknown form %d of k", b, s.form);
+        } else {
+          if (!(s.epsilon > 0.0 && s.epsilon < 0.5)) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: epsilon is not in (0, 0.5)", b);
+          }
+          if (s.ntuning != 2 * d) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: A and D must contain %d probabilities each", b, d);
+          }
+          for (int i = 0; i < 2 * d; ++i)
+            if (!(s.epsilon < s.tuning[i] && s.tuning[i] < 1.0 - s.epsilon)) {
+              delete e;
+              return fail(nullptr, MMB_E_ARG, "block %d: %s must contain %d probabilities in (%g, %g)", b,
+                          i < d ? "A" : "D", d, s.epsilon, 1.0 - s.epsilon);
+            }
+          if (!(s.beta > 0.5 && s.beta <= 1.0)) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: decay is not in (0.5, 1]", b);
+          }
+          if (!(s.target > 0.0 && s.target < 1.0)) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: target is not in (0, 1)", b);
+          }
+        }
+        break;
+      }
       default:
         delete e;
         return fail(nullptr, MMB_E_ARG, "unknown sampler kind %d", s.sampler);
@@ -299,7 +367,7 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
           return fail(nullptr, MMB_E_ARG, "block %d: Dirichlet node %d can be sampled by a SliceSimplex block only", b,
                       s.nodes[a]);
         }
-    if (e->model == MMB_MODEL_IR && s.sampler != MMB_SAMPLER_DGS)
+    if (e->model == MMB_MODEL_IR && s.sampler != MMB_SAMPLER_DGS && !binary_kind(s.sampler))
       for (int a = 0; a < s.nnodes; ++a)
         if (ir_dgs_family(ir->nodes[s.nodes[a]].family)) {
           delete e;
@@ -527,9 +595,12 @@ static void from_device_layout(const mmb_engine* e, const double* dv, double* v)
 int mmb_set_values(mmb_engine* e, const double* values) {
   if (!e || !values) return fail(e, MMB_E_ARG, "null argument");
   if (!e->d_vals) return fail(e, MMB_E_STATE, "mmb_init_chains not called");
-  if (e->model == MMB_MODEL_IR && (e->kinds & (1u << MMB_SAMPLER_DGS))) {
+  constexpr unsigned kDiscreteKinds = (1u << MMB_SAMPLER_DGS) | (1u << MMB_SAMPLER_BMG) | (1u << MMB_SAMPLER_BMC3) |
+                                      (1u << MMB_SAMPLER_BIA);
+  if (e->model == MMB_MODEL_IR && (e->kinds & kDiscreteKinds)) {
     // sampled discrete nodes: every value inside its support, which is what bounds the state-indexed
-    // gathers x[T] (ir.h ev) and the constant-table lookups of the kernels
+    // gathers x[T] (ir.h ev) and the constant-table lookups of the kernels (a binary block's node: 0 or
+    // 1, validatebinary)
     for (const mmb_ir_node& N : e->ir_nodes) {
       if (N.fixed || !ir_dgs_family(N.family)) continue;
       for (int64_t k = 0; k < e->K; ++k)
@@ -593,10 +664,13 @@ static int upload_blocks(mmb_engine* e) {
     d.kind = h.spec.sampler;
     d.nn = h.spec.nnodes;
     d.d = h.d;
-    d.transform = h.spec.sampler == MMB_SAMPLER_SLICE ? h.spec.transform : 1;
+    d.transform = h.spec.sampler == MMB_SAMPLER_SLICE ? h.spec.transform : binary_kind(h.spec.sampler) ? 0 : 1;
     d.form = h.spec.form;
     d.adapt = h.spec.adapt;
     d.batchsize = h.spec.batchsize;
+    // BMG / BMC3: the int k, or the number of index lists (their masks: d.width)
+    if (h.spec.sampler == MMB_SAMPLER_BMG || h.spec.sampler == MMB_SAMPLER_BMC3)
+      d.batchsize = h.spec.form == MMB_BINARY_K_LISTS ? (int32_t)h.tuning.size() : h.spec.nsteps;
     d.sigl_diag = h.sigl_diag;
     // forward differences (the reference's default) unless the analytic gradient was asked for
     d.fdgrad = h.spec.gradient != MMB_GRAD_ANALYTIC ? 1 : 0;
@@ -614,9 +688,11 @@ static int upload_blocks(mmb_engine* e) {
     }
     d.target = h.spec.target;
     d.beta = h.spec.beta;
-    d.scale = h.spec.scale;
+    d.scale = h.spec.sampler == MMB_SAMPLER_BIA ? h.spec.epsilon : h.spec.scale;
     d.width0 = h.tuning.empty() ? 0.0 : h.tuning[0];
     d.width = (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) ? h.width.get() : nullptr;
+    if ((h.spec.sampler == MMB_SAMPLER_BMG || h.spec.sampler == MMB_SAMPLER_BMC3) && h.spec.form == MMB_BINARY_K_LISTS)
+      d.width = h.width.get();
     d.sigl = h.sigl_d;
     d.t_sigma = h.sigma; d.t_accept = h.accept; d.t_m = h.m; d.t_flags = h.flags;
     d.t_Mv = h.Mv; d.t_Mvv = h.Mvv; d.t_Mv_alt = h.Mv_alt; d.t_Mvv_alt = h.Mvv_alt; d.t_Ls = h.Ls; d.t_piv = h.piv; d.t_xnext = h.xnext; d.t_xtag = h.xtag; d.t_nuts = h.nuts; d.t_nfr = h.nfr;
@@ -731,6 +807,24 @@ int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_
     } else if (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) {
       HIPCHK(e, h.width.alloc(h.tuning.size()));
       HIPCHK(e, hipMemcpy(h.width, h.tuning.data(), h.tuning.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else if (binary_kind(h.spec.sampler)) {
+      HIPCHK(e, h.astat.alloc(K * MMB_AMM_STAT_STRIDE));
+      HIPCHK(e, h.astat.zero(K * MMB_AMM_STAT_STRIDE));
+      if (h.spec.sampler == MMB_SAMPLER_BIA) {  // A in sigma, D in accept, iter in m (zeroed above)
+        HIPCHK(e, h.sigma.alloc(K * DP));
+        HIPCHK(e, h.accept.alloc(K * DP));
+        std::vector<double> ta(K * DP, 0.0), td(K * DP, 0.0);
+        for (int64_t k = 0; k < K; ++k)
+          for (int i = 0; i < h.d; ++i) {
+            ta[k * DP + i] = h.tuning[i];
+            td[k * DP + i] = h.tuning[h.d + i];
+          }
+        HIPCHK(e, hipMemcpy(h.sigma, ta.data(), ta.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(h.accept, td.data(), td.size() * sizeof(double), hipMemcpyHostToDevice));
+      } else if (h.spec.form == MMB_BINARY_K_LISTS) {
+        HIPCHK(e, h.width.alloc(h.tuning.size()));
+        HIPCHK(e, hipMemcpy(h.width, h.tuning.data(), h.tuning.size() * sizeof(double), hipMemcpyHostToDevice));
+      }
     }
   }
   if (e->model == MMB_MODEL_LOGISTIC) {
@@ -1401,6 +1495,9 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
       case MMB_SAMPLER_RWM: s += 8.0 * h.d; break;  // scale (read only)
       case MMB_SAMPLER_DGS: break;  // no tune state; the masses stay in registers (samplers.h dgs)
       case MMB_SAMPLER_SLICESIMPLEX: break;  // no tune state; the vertex matrix lives in LDS within one update
+      case MMB_SAMPLER_BIA: s += 8.0 * h.d * 2 + 4.0; break;  // A, D, iter
+      case MMB_SAMPLER_BMG:
+      case MMB_SAMPLER_BMC3: break;  // no tune state
       default: break;
     }
   }
@@ -1437,7 +1534,7 @@ int mmb_amwg_stats(mmb_engine* e, int64_t* out) {
 }
 
 // out[b * width + i]: the first `width` words of block b's astat rows summed over the chains, for the
-// blocks of sampler `kind`
+// blocks of sampler `kind` (RWM: and the BMG, BMC3 and BIA blocks, which count updates and accepts alike)
 static int astat_sums(mmb_engine* e, int kind, int width, int64_t* out) {
   if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
   for (int i = 0; i < MMB_MAX_BLOCKS * width; ++i) out[i] = 0;
@@ -1446,7 +1543,8 @@ static int astat_sums(mmb_engine* e, int kind, int width, int64_t* out) {
   HIPCHK(e, hipStreamSynchronize(e->stream));
   std::vector<uint64_t> h;
   for (size_t b = 0; b < e->blocks.size(); ++b) {
-    if (!e->blocks[b].astat || e->blocks[b].spec.sampler != kind) continue;
+    const int bk = e->blocks[b].spec.sampler;
+    if (!e->blocks[b].astat || !(bk == kind || (kind == MMB_SAMPLER_RWM && binary_kind(bk)))) continue;
     int rc = d2h(e, h, e->blocks[b].astat, (size_t)e->K * MMB_AMM_STAT_STRIDE);
     if (rc) return rc;
     for (int64_t k = 0; k < e->K; ++k)

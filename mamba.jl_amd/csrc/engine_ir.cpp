@@ -232,12 +232,17 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
     if (N.family == MMB_IR_POISSON && !N.fixed)  // (infinite support: no DGS)
       return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: Poisson node %d must be fixed (observed)", n);
     const bool dgs = !N.fixed && ir_dgs_family(N.family);
-    if (dgs) {  // a sampled discrete node: in exactly the DGS blocks, one node each (create_impl), never another kind
+    if (dgs) {  // a sampled discrete node: in DGS blocks or, a binary one, in BMG, BMC3 or BIA blocks, one node
+                // each (create_impl), never another kind
       bool in_dgs = false;
       for (int b = 0; b < spec->nblocks; ++b)
         for (int a = 0; a < spec->blocks[b].nnodes && a < MMB_MAX_NODES_PER_BLOCK; ++a)
           if (spec->blocks[b].nodes[a] == n) {
-            if (spec->blocks[b].sampler != MMB_SAMPLER_DGS)
+            const int bk = spec->blocks[b].sampler;
+            if (binary_kind(bk) && !ir_binary_node(N))
+              return fail(nullptr, MMB_E_ARG, "node IR: %s block %d samples a Bernoulli or DiscreteUniform(0, 1) node; "
+                          "discrete node %d is not binary", binary_name(bk), b, n);
+            if (bk != MMB_SAMPLER_DGS && !binary_kind(bk))
               return fail(nullptr, MMB_E_ARG, "node IR: discrete node %d can be sampled by a DGS block only", n);
             in_dgs = true;
           }
@@ -404,11 +409,21 @@ static const char* const kJitNoDgs = "the specialised kernel declines schemes wi
                                      "nodes and state-indexed gathers are not generated";
 // Nor for SliceSimplex blocks, the Dirichlet density or a Categorical that reads its probabilities
 // from the state
+// Nor for the binary samplers
+static const char* const kJitNoBmg = "the specialised kernel declines schemes with BMG blocks: the binary samplers "
+                                     "are not generated";
+static const char* const kJitNoBmc3 = "the specialised kernel declines schemes with BMC3 blocks: the binary samplers "
+                                      "are not generated";
+static const char* const kJitNoBia = "the specialised kernel declines schemes with BIA blocks: the binary samplers "
+                                     "are not generated";
 static const char* const kJitNoSimplex = "the specialised kernel declines schemes with SliceSimplex blocks and "
                                          "models with a Dirichlet node or a Categorical that reads a sampled P: "
                                          "they are not generated";
 // why the generator declines the scheme (null: it does not)
 static const char* ir_jit_declined(unsigned kinds, const mmb_ir_model* ir) {
+  if (kinds & (1u << MMB_SAMPLER_BMG)) return kJitNoBmg;
+  if (kinds & (1u << MMB_SAMPLER_BMC3)) return kJitNoBmc3;
+  if (kinds & (1u << MMB_SAMPLER_BIA)) return kJitNoBia;
   if (kinds & (1u << MMB_SAMPLER_SLICESIMPLEX)) return kJitNoSimplex;
   for (int n = 0; n < ir->nnodes; ++n)
     if (ir->nodes[n].family == MMB_IR_DIRICHLET || mmb_ir_cat_state(ir->nodes[n].family, ir->nodes[n].cterm) >= 0)

@@ -12,6 +12,9 @@ int tune_len_of(int kind, int d) {
     case MMB_SAMPLER_RWM: return d;   // scale[d]         (RWMTune, rwm.jl:5-9)
     case MMB_SAMPLER_DGS: return 0;   // no tuning state  (DGSTune holds only the mass function, dgs.jl:12-26)
     case MMB_SAMPLER_SLICESIMPLEX: return 0;  // none either (SliceSimplexTune: logf and the constant scale)
+    case MMB_SAMPLER_BMG: return 0;           // none (BMGTune: logf and the constant k, bmg.jl:7-16)
+    case MMB_SAMPLER_BMC3: return 0;          // none (BMC3Tune likewise, bmc3.jl:7-16)
+    case MMB_SAMPLER_BIA: return 1 + 2 * d;   // [iter, A[d], D[d]]  (BIATune, bia.jl:5-25)
     default: return 0;
   }
 }
@@ -127,6 +130,14 @@ int mmb_get_tune(mmb_engine* e, double* tune) {
       if ((rc = d2h(e, sg, h.sigma, K * DP))) return rc;
       for (int64_t k = 0; k < K; ++k)
         for (int i = 0; i < h.d; ++i) tune[k * TL + off + i] = sg[k * DP + i];
+    } else if (h.spec.sampler == MMB_SAMPLER_BIA) {
+      std::vector<double> ta, td;
+      if ((rc = d2h(e, ta, h.sigma, K * DP)) || (rc = d2h(e, td, h.accept, K * DP))) return rc;
+      for (int64_t k = 0; k < K; ++k) {
+        double* t = tune + k * TL + off;
+        t[0] = m[k];
+        for (int i = 0; i < h.d; ++i) { t[1 + i] = ta[k * DP + i]; t[1 + h.d + i] = td[k * DP + i]; }
+      }
     }
     off += h.tune_len;
   }
@@ -143,6 +154,17 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
   // factor); an invalid one is stored with identity positions whatever its pivot bytes hold
   for (int64_t off = 0, b = 0; b < (int64_t)e->blocks.size(); off += e->blocks[b].tune_len, ++b) {
     const auto& h = e->blocks[b];
+    if (h.spec.sampler == MMB_SAMPLER_BIA) {  // bia.jl:41-44: the update takes logs of A - epsilon, 1 - A - epsilon
+      for (int64_t k = 0; k < K; ++k) {
+        const double* t = tune + k * TL + off;
+        bool ok = t[0] >= 0.0 && t[0] < 2147483647.0 && t[0] == (double)(int64_t)t[0];
+        for (int i = 0; i < 2 * h.d; ++i) ok = ok && h.spec.epsilon < t[1 + i] && t[1 + i] < 1.0 - h.spec.epsilon;
+        if (!ok)
+          return fail(e, MMB_E_ARG, "block %d chain %lld: a BIA tune row is [iter, A, D] with iter >= 0 and A, D in "
+                      "(epsilon, 1 - epsilon)", (int)b + 1, (long long)k);
+      }
+      continue;
+    }
     if (h.spec.sampler != MMB_SAMPLER_AMM) continue;
     for (int64_t k = 0; k < K; ++k) {
       const double* t = tune + k * TL + off;
@@ -225,6 +247,14 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
       for (int64_t k = 0; k < K; ++k)
         for (int i = 0; i < h.d; ++i) sg[k * DP + i] = tune[k * TL + off + i];
       if ((rc = h2d(e, h.sigma, sg))) return rc;
+    } else if (h.spec.sampler == MMB_SAMPLER_BIA) {
+      std::vector<double> ta(K * DP, 0.0), td(K * DP, 0.0);
+      for (int64_t k = 0; k < K; ++k) {
+        const double* t = tune + k * TL + off;
+        m[k] = (int32_t)t[0];
+        for (int i = 0; i < h.d; ++i) { ta[k * DP + i] = t[1 + i]; td[k * DP + i] = t[1 + h.d + i]; }
+      }
+      if ((rc = h2d(e, h.sigma, ta)) || (rc = h2d(e, h.accept, td))) return rc;
     }
     if ((rc = h2d(e, h.m, m)) || (rc = h2d(e, h.flags, fl))) return rc;
     off += h.tune_len;

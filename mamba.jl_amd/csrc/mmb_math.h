@@ -43,6 +43,7 @@
 #define MMB_SUB_INIT 4u     /* nutsepsilon momentum (nuts.jl:194) */
 #define MMB_SUB_PROPOSAL 5u /* RWM's non-Normal proposal variates (symdist.h): uniform #(8k + j) for coordinate k */
 #define MMB_SUB_SIMPLEX 6u  /* SliceSimplex's Dirichlet(1, ..., 1) draws: uniform #(32r + j) for element j of draw r */
+#define MMB_SUB_BINARY 7u   /* BMG / BMC3: the index set's uniforms #j; BIA: the proposal uniform #j of element j */
 
 #define MMB_LOG2PI 1.8378770664093454835606594728112352797
 #define MMB_TWOPI_HI 6.28318530717958623200e+00

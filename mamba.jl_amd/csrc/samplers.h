@@ -327,6 +327,175 @@ struct Smp {
     }
   }
 
+  // ---------------------------------------------------------------- BMG, BMC3, BIA
+  // The binary samplers (bmg.jl:57-101, bmc3.jl:57-65, bia.jl:70-119) of the block's one Bernoulli or
+  // DiscreteUniform(0, 1) node of n = B.d <= 32 elements (node-IR models), element i on lane i.
+  // logf(x) is M::logf: logpdf!(block, x), the node's own term and its targets in the block's term
+  // order, with the early exit on a non-finite running sum; the targets' element terms are evaluated
+  // by all 32 lanes.  The two chains of a wave take their branches on their own, and every cross-lane
+  // step (the 32-wide shuffles, lane_value, the DPP sums inside logf) stays within the chain's own 32
+  // lanes.  Element sets are 32-bit masks, bit i for element i.  rb is the block's MMB_SUB_BINARY
+  // stream, ru its MMB_SUB_UNIFORM stream.  Updates and accepts are counted as RWM's (mmb_rwm_stats).
+  //
+  // The index set (randind; the reference's StatsBase.sample cannot be restated):
+  //   int k    a partial Fisher-Yates shuffle of 0..n-1, position p on lane p: for j = 0..k-1,
+  //            r = j + min(floor(u_j (n - j)), n - j - 1), u_j = uniform #j of rb, swap positions j and r;
+  //            the set is the first k positions
+  //   lists    list number min(floor(u_0 m), m - 1) of the m lists (B.width: one mask per list)
+  __device__ __forceinline__ static uint32_t bin_index_set(const DBlock& B, const mmb_rng& rb, const Grp<G>& g) {
+    const int n = B.d < 32 ? B.d : 32;
+    const uint32_t all = n >= 32 ? 0xffffffffu : (1u << n) - 1u;
+    if (B.form == MMB_BINARY_K_LISTS) {
+      const int m = B.batchsize;
+      int q = (int)(mmb_uniform(&rb, 0u) * (double)m);
+      q = q < m - 1 ? q : m - 1;
+      q = q > 0 ? q : 0;
+      return (uint32_t)B.width[q] & all;
+    }
+    const int k = B.batchsize < n ? B.batchsize : n;
+    int perm = g.lane;
+    uint32_t set = 0u;
+    for (int j = 0; j < k; ++j) {
+      const int left = n - j;
+      int t = (int)(mmb_uniform(&rb, (uint32_t)j) * (double)left);
+      t = t < left - 1 ? t : left - 1;
+      const int r = j + (t > 0 ? t : 0);
+      const int pr = __shfl(perm, r, 32), pj = __shfl(perm, j, 32);
+      perm = g.lane == j ? pr : (g.lane == r ? pj : perm);
+      set |= 1u << (uint32_t)(pr & 31);
+    }
+    return set & all;
+  }
+  __device__ __forceinline__ static void bin_count(const DBlock& B, int c, bool acc, const Grp<G>& g) {
+    if (g.lane == 0 && B.t_astat != nullptr) {
+      uint64_t* a = B.t_astat + (size_t)c * MMB_AMM_STAT_STRIDE;
+      (void)__hip_atomic_fetch_add(a + 0, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (acc) (void)__hip_atomic_fetch_add(a + 1, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  // t_i summed over the elements i of `set` in ascending order, t_i on lane i
+  __device__ __forceinline__ static double bin_set_sum(double t, uint32_t set) {
+    double q = 0.0;
+    for (uint32_t rem = set; rem != 0u; rem &= rem - 1u) q = q + __shfl(t, (int)__builtin_ctz(rem), 32);
+    return q;
+  }
+
+  // BMC3 (bmc3.jl:57-65): the elements of the index set are flipped, and the candidate x is accepted iff
+  // u < exp(logf(x) - logf(v)), u = uniform #0 of ru.  Two evaluations of logf.  A NaN ratio rejects.
+  __device__ __forceinline__ static void bmc3(const SweepArgs& A, const DBlock& B, int c, const mmb_rng& ru,
+                                              const mmb_rng& rb, St& s, const Lc& l, const Grp<G>& g) {
+    static_assert(G == 32 && R == 1, "the binary samplers keep one element per lane of a 32-lane group");
+    double v[R], x[R];
+    M::unlist(B, s, g.lane, v);
+    const uint32_t set = bin_index_set(B, rb, g);
+    x[0] = ((set >> (uint32_t)g.lane) & 1u) != 0u ? 1.0 - v[0] : v[0];
+    const double lx = M::logf(A, B, s, l, g, x);
+    const double lv = M::logf(A, B, s, l, g, v);
+    const bool acc = mmb_uniform(&ru, 0u) < mmb_exp(lx - lv);
+    if (acc) v[0] = x[0];
+    bin_count(B, c, acc, g);
+    M::relist(B, s, g, v);
+  }
+
+  // BMG's pbernoulli! (bmg.jl:62-77) at x, lf = logf(x): for each i of the set, ascending,
+  // p_i = invlogit(logf(x | x_i = 1) - logf(x | x_i = 0)), replaced by 0.5 unless 0 < p_i < 1 (a NaN
+  // fails that test too).  One of the two configurations is x itself, so each i costs one evaluation
+  // of logf, at x with element i flipped; the reference evaluates both, which gives the same values
+  // because logf is a deterministic function of the state.  Lane i keeps p_i in a register, as DGS
+  // keeps its masses; nothing goes to memory.
+  __device__ static double bmg_probs(const SweepArgs& A, const DBlock& B, const St& s, const Lc& l, const Grp<G>& g,
+                                     const double* x, double lf, uint32_t set) {
+    double p = 0.5;
+    for (uint32_t rem = set; rem != 0u; rem &= rem - 1u) {
+      const int i = (int)__builtin_ctz(rem);
+      const double xi = __shfl(x[0], i, 32);
+      double y[R];
+      y[0] = g.lane == i ? 1.0 - x[0] : x[0];
+      const double lo = M::logf(A, B, s, l, g, y);
+      const double pi = mmb_invlogit(xi == 1.0 ? lf - lo : lo - lf);
+      p = g.lane == i ? ((0.0 < pi && pi < 1.0) ? pi : 0.5) : p;
+    }
+    return p;
+  }
+  // BMG (bmg.jl:57-101): theta_i = (uniform #(1 + i) of ru < p_i) for i in the set, y = x with theta
+  // written in, qy = sum_i log(y_i == 1 ? p_i : 1 - p_i) with p at x, qx the same for x with p at y (both
+  // over the set in ascending order), accepted iff u < exp((logf(y) - qy) - (logf(x) - qx)), u = uniform
+  // #0 of ru.  n = 1 takes the reference's direct branch: theta is the new value, no accept step (counted
+  // as accepted).  k + 1 evaluations of logf for x and k + 1 for y: 2k + 2 against the reference's 4k + 2.
+  __device__ __forceinline__ static void bmg(const SweepArgs& A, const DBlock& B, int c, const mmb_rng& ru,
+                                             const mmb_rng& rb, St& s, const Lc& l, const Grp<G>& g) {
+    static_assert(G == 32 && R == 1, "the binary samplers keep one element per lane of a 32-lane group");
+    double v[R], y[R];
+    M::unlist(B, s, g.lane, v);
+    const uint32_t set = bin_index_set(B, rb, g);
+    const bool in = ((set >> (uint32_t)g.lane) & 1u) != 0u;
+    const double lfx = M::logf(A, B, s, l, g, v);
+    const double px = bmg_probs(A, B, s, l, g, v, lfx, set);
+    const double theta = mmb_uniform(&ru, 1u + (uint32_t)g.lane) < px ? 1.0 : 0.0;
+    y[0] = in ? theta : v[0];
+    bool acc = true;
+    if (B.d > 1) {
+      const double qy = bin_set_sum(y[0] == 1.0 ? mmb_log(px) : mmb_log(1.0 - px), set);
+      const double lfy = M::logf(A, B, s, l, g, y);
+      const double py = bmg_probs(A, B, s, l, g, y, lfy, set);
+      const double qx = bin_set_sum(v[0] == 1.0 ? mmb_log(py) : mmb_log(1.0 - py), set);
+      acc = mmb_uniform(&ru, 0u) < mmb_exp((lfy - qy) - (lfx - qx));
+    }
+    if (acc) v[0] = y[0];
+    bin_count(B, c, acc, g);
+    M::relist(B, s, g, v);
+  }
+
+  // BIA (bia.jl:70-119).  Lane j proposes for element j with u_j = uniform #j of rb: a 0 becomes 1 iff
+  // u_j < A_j (added), a 1 becomes 0 iff u_j < D_j (deleted); q_ratio is the product over j ascending of
+  // D_j / A_j (added), A_j / D_j (deleted), 1 (kept); alpha = min(1, exp(logf(x) - logf(v)) q_ratio).
+  // Then A_j and D_j adapt (bia.jl:101-111; every j, whether it moved or not), with iter^(-decay) as
+  // exp(-decay log(iter)), and the proposal is accepted iff uniform #0 of ru < alpha.  The adaptation
+  // never switches off (the reference has no adapt flag here).  Tune per chain: iter (B.t_m), A
+  // (B.t_sigma), D (B.t_accept); epsilon = B.scale, decay = B.beta, target = B.target.
+  // A NaN alpha would turn every A_j and D_j into NaN in the reference (0 * NaN) and the sampler would
+  // be dead from then on; here it rejects and leaves the tune row, iter included, as it was.
+  __device__ __forceinline__ static void bia(const SweepArgs& A, const DBlock& B, int c, const mmb_rng& ru,
+                                             const mmb_rng& rb, St& s, const Lc& l, const Grp<G>& g) {
+    static_assert(G == 32 && R == 1, "the binary samplers keep one element per lane of a 32-lane group");
+    const int d = B.d < 32 ? B.d : 32;
+    const bool in = g.lane < d;
+    double v[R], x[R];
+    M::unlist(B, s, g.lane, v);
+    const size_t at = (size_t)c * DP + (size_t)g.lane;
+    const double Aj = in ? B.t_sigma[at] : 0.5, Dj = in ? B.t_accept[at] : 0.5;
+    const int iter = B.t_m[c] + 1;
+    const double eps = B.scale;
+    const double uj = mmb_uniform(&rb, (uint32_t)g.lane);
+    const bool add = in && v[0] == 0.0 && uj < Aj;
+    const bool del = in && v[0] != 0.0 && uj < Dj;
+    x[0] = add ? 1.0 : (del ? 0.0 : v[0]);
+    const double f = add ? Dj / Aj : (del ? Aj / Dj : 1.0);
+    double q = 1.0;
+    for (int j = 0; j < d; ++j) q = q * lane_value(f, j);
+    const double lx = M::logf(A, B, s, l, g, x);
+    const double lv = M::logf(A, B, s, l, g, v);
+    const double r = mmb_exp(lx - lv) * q;
+    bool acc = false;
+    if (r == r) {
+      const double alpha = r < 1.0 ? r : 1.0;
+      const double gn = mmb_exp(-B.beta * mmb_log((double)iter));
+      if (in) {
+        const double ca = mmb_log((Aj - eps) / (1.0 - Aj - eps)) + gn * (add ? 1.0 : 0.0) * (alpha - B.target);
+        const double ea = mmb_exp(ca);
+        B.t_sigma[at] = (ea * (1.0 - eps) + eps) / (1.0 + ea);
+        const double cd = mmb_log((Dj - eps) / (1.0 - Dj - eps)) + gn * (del ? 1.0 : 0.0) * (alpha - B.target);
+        const double ed = mmb_exp(cd);
+        B.t_accept[at] = (ed * (1.0 - eps) + eps) / (1.0 + ed);
+      }
+      if (g.lane == 0) B.t_m[c] = iter;
+      acc = mmb_uniform(&ru, 0u) < alpha;
+    }
+    if (acc) v[0] = x[0];
+    bin_count(B, c, acc, g);
+    M::relist(B, s, g, v);
+  }
+
   // ---------------------------------------------------------------- SliceSimplex
   // slicesimplex.jl:86-122 (sample!, makefirstsimplex, shrinksimplex) for the block's one Dirichlet node
   // of k = B.d <= 32 elements (node-IR models; M::ssx_* in ir.h), the reference's linear solves

@@ -162,6 +162,16 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
             S::slice_simplex(A, B, ru, rs, s, g, M::ssx_rows(A, lds));
           }
           break;
+        case MMB_SAMPLER_BMG:
+        case MMB_SAMPLER_BMC3:
+        case MMB_SAMPLER_BIA:
+          if constexpr ((KINDS >> MMB_SAMPLER_BMG) & 1u) {
+            const mmb_rng rb = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_BINARY);
+            if (B.kind == MMB_SAMPLER_BMG) S::bmg(A, B, c, ru, rb, s, l, g);
+            else if (B.kind == MMB_SAMPLER_BMC3) S::bmc3(A, B, c, ru, rb, s, l, g);
+            else S::bia(A, B, c, ru, rb, s, l, g);
+          }
+          break;
         case MMB_SAMPLER_GIBBS: if constexpr ((KINDS >> MMB_SAMPLER_GIBBS) & 1u) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
           const mmb_rng gu = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_U);
@@ -231,4 +241,6 @@ constexpr unsigned K_RWM = 1u << MMB_SAMPLER_RWM;
 constexpr unsigned K_DGS = 1u << MMB_SAMPLER_DGS;
 // SliceSimplex likewise: the instantiation that schemes with such a block take holds every other kind
 constexpr unsigned K_SIMPLEX = 1u << MMB_SAMPLER_SLICESIMPLEX;
+// The binary samplers BMG, BMC3 and BIA likewise: one instantiation for the three, which holds every other kind
+constexpr unsigned K_BIN = (1u << MMB_SAMPLER_BMG) | (1u << MMB_SAMPLER_BMC3) | (1u << MMB_SAMPLER_BIA);
 

@@ -25,6 +25,9 @@ Uniform (constant bounds), Beta for sampled nodes; Binomial, Poisson, Bernoulli,
 DiscreteUniform for fixed nodes; + - * / neg abs exp log sqrt invlogit logit, x**2; blocks of
 <= 32 elements.
 
+Binary nodes (src/samplers/bmg.jl, bmc3.jl, bia.jl): a Bernoulli or DiscreteUniform(0, 1) node of at most 32
+elements may instead be sampled by one `BMG`, `BMC3` or `BIA` block, which holds that node alone.
+
 Discrete nodes (src/samplers/dgs.jl): a Bernoulli, Binomial (n data), Categorical(p) (p a constant
 list or a data vector shared by every element, support 1..K) or DiscreteUniform(a, b) (constant
 integer bounds) node may be sampled, by a `DGS` block only; Poisson stays observed (infinite
@@ -421,7 +424,8 @@ class Model(_BaseModel):
                 raise ArgumentError(f"incompatible initial value for node : {n}")
             self.lens[n] = v.size
         self.fixed_vals = {n: self._initval(init0, n) for n in self.fixed}
-        by_dgs = {p for s in self.samplers if s.kind == abi.MMB_SAMPLER_DGS for p in s.params}
+        binary = (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA)
+        by_dgs = {p for s in self.samplers if s.kind == abi.MMB_SAMPLER_DGS or s.kind in binary for p in s.params}
         for s in self.samplers:
             for n in s.params:
                 fam = self.traced[n].fam
@@ -429,6 +433,12 @@ class Model(_BaseModel):
                     if fam not in _DGS_FAMILIES:
                         raise ArgumentError(f"DGS: node {n} is not a Bernoulli, Binomial, Categorical or "
                                             "DiscreteUniform node")
+                elif s.kind in binary:
+                    # validatebinary's domain: Bernoulli, or DiscreteUniform(0, 1) (bmg.jl:26-37, bia.jl:49)
+                    d = self.traced[n]
+                    if not (fam == abi.MMB_IR_BERNOULLI or
+                            (fam == abi.MMB_IR_DISCRETEUNIFORM and (d.lo, d.hi) == (0, 1))):
+                        raise ArgumentError(f"{s.name}: node {n} is not a Bernoulli or DiscreteUniform(0, 1) node")
                 elif s.kind == abi.MMB_SAMPLER_SLICESIMPLEX:
                     if fam != abi.MMB_IR_DIRICHLET:
                         raise ArgumentError(f"SliceSimplex: node {n} is not a Dirichlet node")

@@ -171,6 +171,18 @@ class Engine:
                       "rate": v[2 * b + 1] / v[2 * b] if v[2 * b] else float("nan")}
         return out
 
+    def accept_stats(self):
+        """Update and accept counters since init_chains of every block that has a Metropolis accept step
+        and counts it (mmb_rwm_stats): RWM, BMG, BMC3 and BIA blocks, one dict per block keyed by block
+        index, summed over the chains.  A BMG block of one element has no accept step (bmg.jl:83-84):
+        every update counts as accepted."""
+        kinds = (abi.MMB_SAMPLER_RWM, abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA)
+        v = (C.c_int64 * (abi.MMB_MAX_BLOCKS * 2))()
+        self._chk(self.lib.mmb_rwm_stats(self.h, v))
+        return {b: {"updates": v[2 * b], "accepts": v[2 * b + 1],
+                    "rate": v[2 * b + 1] / v[2 * b] if v[2 * b] else float("nan")}
+                for b, blk in enumerate(self.model.samplers) if getattr(blk, "kind", None) in kinds}
+
     def amwg_stats(self):
         """AMWG block updates since init_chains that ran the sequential coordinate loop
         (mmb_amwg_stats) rather than the lane-parallel decision of every coordinate."""

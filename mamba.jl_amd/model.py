@@ -48,6 +48,8 @@ class Model:
         for s in samplers:
             if s.kind == abi.MMB_SAMPLER_DGS:
                 raise ArgumentError("DGS samples the discrete nodes of node-IR models (ir.Model) only")
+            if s.kind in (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA):
+                raise ArgumentError(f"{s!r} samples the binary nodes of node-IR models (ir.Model) only")
             if s.kind == abi.MMB_SAMPLER_SLICESIMPLEX:
                 raise ArgumentError("SliceSimplex samples the Dirichlet nodes of node-IR models (ir.Model) only")
             if len(s.params) > abi.MMB_MAX_NODES_PER_BLOCK:

@@ -15,6 +15,10 @@ Argument meaning, defaults and validation errors follow the reference:
                   (node-IR models; no tuning, nothing adapts)
   SliceSimplex(params, scale=1.0)  -- slice sampling of Dirichlet nodes on the simplex
                   (node-IR models; no tuning, nothing adapts)   src/samplers/slicesimplex.jl:24-58
+  BMG(params, k=1), BMC3(params, k=1)  -- binary Metropolised Gibbs and binary MC3 on one Bernoulli
+                  node (node-IR models; no tuning)            src/samplers/bmg.jl:42-50, bmc3.jl:42-50
+  BIA(params, A, D, epsilon, decay=0.55, target=0.45)  -- binary individual adaptation; A and D
+                  always adapt (node-IR models)               src/samplers/bia.jl:18-24, bia.jl:55-63
   Gibbs(params)  -- a user `Sampler(params, f)` whose f is the node's conjugate full
                     conditional (doc/tutorial/line.jl:27-45); lowered per model.
 """
@@ -82,6 +86,30 @@ class Sampler:
             raise ArgumentError(f"Sigma dimension differs from variate length {dim}")
         if self.kind == abi.MMB_SAMPLER_RWM and not (t.size == 1 or t.size == dim):  # rwm.jl:39-44
             raise ArgumentError(f"length(scale) differs from variate length {dim}")
+        if self.kind in (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3):  # bmg.jl:26-37, bmc3.jl:26-37
+            if isinstance(self.k, int):
+                if self.k > dim:
+                    raise ArgumentError(f"k exceeds variate length {dim}")
+            elif max(max(ix) for ix in self.k) > dim:
+                raise ArgumentError(f"indices in k exceed variate length {dim}")
+            self.tuning = None if isinstance(self.k, int) else np.array(
+                [float(sum({1 << (i - 1) for i in ix})) for ix in self.k])
+        if self.kind == abi.MMB_SAMPLER_BIA:  # bia.jl:18-24 (defaults), bia.jl:36-50 (validate)
+            a, dd, eps = self.bia
+            eps = 0.01 / dim if eps is None else float(eps)
+            a = np.full(dim, 1.0 / dim) if a is None else np.atleast_1d(np.asarray(a, dtype=np.float64)).ravel()
+            dd = np.full(dim, 1.0 / dim) if dd is None else np.atleast_1d(np.asarray(dd, dtype=np.float64)).ravel()
+            if not 0.0 < eps < 0.5:
+                raise ArgumentError("epsilon is not in (0, 0.5)")
+            for nm, v in (("A", a), ("D", dd)):
+                if not (v.size == dim and np.all((eps < v) & (v < 1.0 - eps))):
+                    raise ArgumentError(f"{nm} must contain {dim} probabilities in ({eps}, {1.0 - eps})")
+            if not 0.5 < self.beta <= 1.0:
+                raise ArgumentError("decay is not in (0.5, 1]")
+            if not 0.0 < self.target < 1.0:
+                raise ArgumentError("target is not in (0, 1)")
+            self.epsilon = eps
+            self.tuning = np.concatenate([a, dd])
 
     def spec_tuning(self, dim):
         """`tuning` as the block spec carries it: RWM's scalar scale is broadcast to the variate length
@@ -91,9 +119,12 @@ class Sampler:
         return self.tuning
 
     def __repr__(self):
-        names = {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS",
-                 10: "SliceSimplex"}
-        return f"{names[self.kind]}({self.params})"
+        return f"{self.name}({self.params})"
+
+    @property
+    def name(self):
+        return {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS",
+                10: "SliceSimplex", 11: "BMG", 12: "BMC3", 13: "BIA"}[self.kind]
 
 
 def AMWG(params, sigma, adapt="all", batchsize=50, target=0.44):
@@ -200,6 +231,66 @@ def SliceSimplex(params, scale=1.0):
     if not 0.0 < sc <= 1.0:
         raise ArgumentError("scale is not in (0, 1]")
     return Sampler(params, abi.MMB_SAMPLER_SLICESIMPLEX, abi.MMB_ADAPT_NONE, None, scale=sc)
+
+
+def _binary(name, kind, params, k):
+    params = _params(params)
+    if len(params) != 1:
+        raise ArgumentError(f"{name}({params}) is one joint step over all the listed nodes in the reference, which a "
+                            f"block of one node cannot restate: give {name} one node (one block per node is a "
+                            "different sampler)")
+    if isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+        k = int(k)
+        if k < 1:
+            raise ArgumentError("k must be at least 1")
+        s = Sampler(params, kind, abi.MMB_ADAPT_NONE, None, form=abi.MMB_BINARY_K_INT, nsteps=k)
+    else:
+        try:
+            ok = all(float(i) == int(i) and not isinstance(i, bool) for ix in k for i in ix)
+            k = [[int(i) for i in ix] for ix in k]
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or any(len(ix) == 0 for ix in k):
+            raise ArgumentError("k is an int or a list of non-empty lists of 1-based indices")
+        if not 1 <= len(k) <= abi.MMB_BINARY_MAX_LISTS:
+            raise ArgumentError(f"k holds 1..{abi.MMB_BINARY_MAX_LISTS} index lists")
+        if min(min(ix) for ix in k) < 1:
+            raise ArgumentError("indices in k start at 1")
+        s = Sampler(params, kind, abi.MMB_ADAPT_NONE, None, form=abi.MMB_BINARY_K_LISTS)
+    s.k = k
+    return s
+
+
+def BMG(params, k=1):
+    """BMG(params; k=1) -- bmg.jl:42-50: binary Metropolised Gibbs on the one Bernoulli (or DiscreteUniform(0, 1))
+    node of `params`, 1..32 elements.  k is the number of elements drawn without replacement for each
+    update, or a list of 1-based index lists of which one is drawn (BMGForm, bmg.jl:5).  Node-IR models
+    only.  No tuning state."""
+    return _binary("BMG", abi.MMB_SAMPLER_BMG, params, k)
+
+
+def BMC3(params, k=1):
+    """BMC3(params; k=1) -- bmc3.jl:42-50: binary MC3, the elements of the drawn index set are flipped together;
+    k as for BMG (BMC3Form, bmc3.jl:5).  Node-IR models only.  No tuning state."""
+    return _binary("BMC3", abi.MMB_SAMPLER_BMC3, params, k)
+
+
+def BIA(params, A=None, D=None, epsilon=None, decay=0.55, target=0.45):
+    """BIA(params; A, D, epsilon, decay=0.55, target=0.45) -- bia.jl:55-63: binary individual adaptation.  The
+    defaults are the reference's (bia.jl:18-24): A = D = 1 / n and epsilon = 0.01 / n for a node of n
+    elements, so they and validate (bia.jl:36-50) are resolved once n is known (setinits); the
+    default A = 1 / n does not pass validate for n = 1, as in the reference.  A and D adapt at every
+    update; tune row [iter, A[n], D[n]].  Node-IR models only."""
+    params = _params(params)
+    if len(params) != 1:
+        raise ArgumentError(f"BIA({params}) is one joint step over all the listed nodes in the reference, which a "
+                            "block of one node cannot restate: give BIA one node")
+    try:
+        s = Sampler(params, abi.MMB_SAMPLER_BIA, abi.MMB_ADAPT_NONE, None, beta=decay, target=target)
+    except (TypeError, ValueError):
+        raise ArgumentError("decay and target are numbers") from None
+    s.bia = (A, D, epsilon)
+    return s
 
 
 def Gibbs(params):
