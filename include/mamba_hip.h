@@ -98,11 +98,18 @@ typedef enum {
    * the initial A[dim] then D[dim] in tuning; tune row [iter, A[dim], D[dim]]. */
   MMB_SAMPLER_BMG = 11,  /* src/samplers/bmg.jl:57-101: binary Metropolised Gibbs */
   MMB_SAMPLER_BMC3 = 12, /* src/samplers/bmc3.jl:57-65: binary MC3 */
-  MMB_SAMPLER_BIA = 13   /* src/samplers/bia.jl:70-119: binary individual adaptation */
+  MMB_SAMPLER_BIA = 13,  /* src/samplers/bia.jl:70-119: binary individual adaptation */
+  /* BHMC of one such node (additive too): traveltime in mmb_block_spec.scale, finite, > 0 and
+   * <= MMB_BHMC_MAX_TRAVELTIME; refresh in form (0: the reference, the velocity is never redrawn; 1: it is
+   * redrawn at the start of every update).  Tune row [position[dim], velocity[dim], wallhits, wallcrosses,
+   * initialised]; a chain whose `initialised` is 0 draws its particle at its first update. */
+  MMB_SAMPLER_BHMC = 14  /* src/samplers/bhmc.jl:35-122: binary Hamiltonian Monte Carlo */
 } mmb_sampler_kind;
 typedef enum { MMB_BINARY_K_INT = 0, MMB_BINARY_K_LISTS = 1 } mmb_binary_form;
 #define MMB_BINARY_MAX_LISTS 64
 #define MMB_BINARY_MAX 32
+/* 128 pi: an update has at most dim (floor(traveltime / pi) + 2) wall events, so the cap bounds it by 4160 */
+#define MMB_BHMC_MAX_TRAVELTIME 402.1238596594935
 
 typedef enum { MMB_ADAPT_ALL = 0, MMB_ADAPT_BURNIN = 1, MMB_ADAPT_NONE = 2 } mmb_adapt;
 typedef enum { MMB_SLICE_MULTIVARIATE = 0, MMB_SLICE_UNIVARIATE = 1 } mmb_slice_form;
@@ -132,12 +139,12 @@ typedef struct {
   int32_t nodes[MMB_MAX_NODES_PER_BLOCK];  /* node ids in block (params) order */
   int32_t adapt;                           /* AMWG/AMM: mmb_adapt (default :all) */
   int32_t form;                            /* Slice: mmb_slice_form (default Multivariate); RWM: mmb_rwm_proposal;
-                                              BMG/BMC3: mmb_binary_form */
+                                              BMG/BMC3: mmb_binary_form; BHMC: refresh (0 or 1) */
   int32_t transform;                       /* Slice: transform flag (default false); AMWG/AMM/NUTS/RWM use true */
   int32_t batchsize;                       /* AMWG batchsize (default 50) */
   double target;                           /* AMWG target (0.44) / NUTS target (0.6) / BIA target (0.45) */
   double beta;                             /* AMM beta (0.05); BIA decay (0.55) */
-  double scale;                            /* AMM scale (2.38); SliceSimplex scale in (0, 1] */
+  double scale;                            /* AMM scale (2.38); SliceSimplex scale in (0, 1]; BHMC traveltime */
   int32_t dim;                             /* unlisted block length (checked by mmb_create) */
   int32_t ntuning;                         /* length of `tuning` */
   const double* tuning;                    /* AMWG sigma[dim] | Slice width[dim] | RWM scale[dim] | AMM Sigma[dim*dim] col-major
@@ -196,8 +203,8 @@ typedef enum {
 #define MMB_SIMPLEX_MAX 32
 #define MMB_IR_CAT_STATE(off) (-2 - (off))
 /* A sampled discrete node (Bernoulli, Binomial, Categorical, DiscreteUniform) is updated by a DGS block, or, when
- * it is binary (Bernoulli, DiscreteUniform(0, 1)) and has at most MMB_BINARY_MAX elements, by a BMG, BMC3 or BIA
- * block; each such block holds exactly one such node.  Its support is the integers lo..hi (Binomial: 0..n_i of
+ * it is binary (Bernoulli, DiscreteUniform(0, 1)) and has at most MMB_BINARY_MAX elements, by a BMG, BMC3, BIA or
+ * BHMC block; each such block holds exactly one such node.  Its support is the integers lo..hi (Binomial: 0..n_i of
  * element i), at most MMB_DGS_MAX_SUPPORT values.  Off the support its log density is -Inf. */
 #define MMB_DGS_MAX_SUPPORT 32
 
@@ -631,7 +638,8 @@ int mmb_amwg_stats(mmb_engine* e, int64_t* out /* 1 */);
  * over the engine's chains: out[2 b] = block updates, out[2 b + 1] = accepted ones (rwm.jl:67-70).
  * A user sizes `scale` from this acceptance rate (RWM does not adapt).  BMG, BMC3 and BIA blocks fill
  * their rows the same way (a BMG block of one element has no accept step: every update counts as
- * accepted).  Diagnostics only. */
+ * accepted), and so do BHMC blocks, whose accepts are the updates that ran to traveltime (the others
+ * stalled and changed nothing).  Diagnostics only. */
 int mmb_rwm_stats(mmb_engine* e, int64_t* out /* MMB_MAX_BLOCKS x 2 */);
 
 /* The lane-group slot -> chain table the next window will run with (K entries; the identity

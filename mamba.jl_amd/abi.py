@@ -23,6 +23,9 @@ MMB_SUB_SIMPLEX = 6  # csrc/mmb_math.h: the Dirichlet(1, ..., 1) draws of a Slic
 MMB_SAMPLER_BMG, MMB_SAMPLER_BMC3, MMB_SAMPLER_BIA = 11, 12, 13  # the binary samplers: additive too
 MMB_BINARY_K_INT, MMB_BINARY_K_LISTS = 0, 1  # mmb_block_spec.form of BMG / BMC3
 MMB_BINARY_MAX_LISTS, MMB_BINARY_MAX = 64, 32
+MMB_SAMPLER_BHMC = 14  # binary Hamiltonian Monte Carlo: additive too
+MMB_BHMC_MAX_TRAVELTIME = 402.1238596594935  # 128 pi: bounds an update's wall events
+MMB_SUB_NORMAL, MMB_SUB_INIT = 0, 4  # csrc/mmb_math.h: BHMC's refreshed velocities / its first particle
 MMB_SUB_BINARY = 7  # csrc/mmb_math.h: index-set uniforms of BMG / BMC3, proposal uniforms of BIA
 (MMB_RWM_NORMAL, MMB_RWM_SYMUNIFORM, MMB_RWM_SYMTRIANGULAR, MMB_RWM_EPANECHNIKOV, MMB_RWM_BIWEIGHT,
  MMB_RWM_TRIWEIGHT, MMB_RWM_COSINE) = range(7)

@@ -15,6 +15,7 @@
 #include "mamba_hip.h"
 #include "mmb_math.h"
 #include "symdist.h"
+#include "bhmc.h"
 #include "ir_math.h"
 
 #define MMB_MAXB MMB_MAX_BLOCKS
@@ -136,10 +137,11 @@ struct DBlock {
                          //       with the factor still in registers), valid when t_xtag[c] matches
   int64_t* t_xtag;       // AMM   [K] (xepoch << 32) | iteration the carried proposal is for
   uint64_t* t_astat;     // AMM   [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats), diagnostics;
-                         // RWM, BMG, BMC3, BIA   the same rows: [0] updates, [1] accepts (mmb_rwm_stats)
+                         // RWM, BMG, BMC3, BIA, BHMC   the same rows: [0] updates, [1] accepts (mmb_rwm_stats)
   double* t_nuts;        // NUTS  [K][8] eps, epsbar, Hbar, mu, alpha, nalpha, -, -
   double* t_nfr;         // NUTS  [K][NutsFrames<DV>::DBL] tree frames (scratch, nuts.h)
-  double* t_hmc;         // HMC/MALA [K][2] epsilon, L (HMCTune / MALATune, hmc.jl:5-28)
+  double* t_hmc;         // HMC/MALA [K][2] epsilon, L (HMCTune / MALATune, hmc.jl:5-28); BHMC [K][2] wallhits,
+                         // wallcrosses (BHMCTune; t_sigma: position, t_accept: velocity, t_m: initialised)
   int32_t ir_blk;        // node IR: index into SweepArgs::ir_blocks
   int32_t fdgrad;        // NUTS/HMC/MALA on line: 1 = Calculus forward differences (mmb_gradient)
   const int32_t* sep;    // node-IR AMWG block whose logpdf! separates by coordinate (engine.cpp ir_sep_table):

@@ -291,7 +291,8 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
         break;
       case MMB_SAMPLER_BMG:
       case MMB_SAMPLER_BMC3:
-      case MMB_SAMPLER_BIA: {  // bmg.jl:26-37, bmc3.jl:26-37, bia.jl:36-50 (validate): one binary node per block
+      case MMB_SAMPLER_BIA:
+      case MMB_SAMPLER_BHMC: {  // bmg.jl:26-37, bmc3.jl:26-37, bia.jl:36-50, bhmc.jl:30 (validate): one binary node per block
         const char* nm = binary_name(s.sampler);
         if (e->model != MMB_MODEL_IR) {
           delete e;
@@ -312,7 +313,18 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
           return fail(nullptr, MMB_E_ARG, "block %d: a %s block holds a node of 1..%d elements", b, nm, MMB_BINARY_MAX);
         }
         const double all = d >= 32 ? 4294967295.0 : (double)((1u << d) - 1u);
-        if (s.sampler != MMB_SAMPLER_BIA && s.form == MMB_BINARY_K_INT) {
+        if (s.sampler == MMB_SAMPLER_BHMC) {
+          // the cap bounds an update's wall events (samplers.h bhmc): a documented refusal
+          if (!(std::isfinite(s.scale) && s.scale > 0.0 && s.scale <= MMB_BHMC_MAX_TRAVELTIME)) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: traveltime is not finite, > 0 and <= %g (128 pi)", b,
+                        (double)MMB_BHMC_MAX_TRAVELTIME);
+          }
+          if (s.form != 0 && s.form != 1) {
+            delete e;
+            return fail(nullptr, MMB_E_ARG, "block %d: refresh is 0 or 1", b);
+          }
+        } else if (s.sampler != MMB_SAMPLER_BIA && s.form == MMB_BINARY_K_INT) {
           if (s.nsteps < 1 || s.nsteps > d) {
             delete e;
             return fail(nullptr, MMB_E_ARG, "block %d: k exceeds variate length %d", b, d);
@@ -596,7 +608,7 @@ int mmb_set_values(mmb_engine* e, const double* values) {
   if (!e || !values) return fail(e, MMB_E_ARG, "null argument");
   if (!e->d_vals) return fail(e, MMB_E_STATE, "mmb_init_chains not called");
   constexpr unsigned kDiscreteKinds = (1u << MMB_SAMPLER_DGS) | (1u << MMB_SAMPLER_BMG) | (1u << MMB_SAMPLER_BMC3) |
-                                      (1u << MMB_SAMPLER_BIA);
+                                      (1u << MMB_SAMPLER_BIA) | (1u << MMB_SAMPLER_BHMC);
   if (e->model == MMB_MODEL_IR && (e->kinds & kDiscreteKinds)) {
     // sampled discrete nodes: every value inside its support, which is what bounds the state-indexed
     // gathers x[T] (ir.h ev) and the constant-table lookups of the kernels (a binary block's node: 0 or
@@ -821,6 +833,15 @@ int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_
           }
         HIPCHK(e, hipMemcpy(h.sigma, ta.data(), ta.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(h.accept, td.data(), td.size() * sizeof(double), hipMemcpyHostToDevice));
+      } else if (h.spec.sampler == MMB_SAMPLER_BHMC) {
+        // position in sigma, velocity in accept, wallhits and wallcrosses in hmc, initialised in m (zeroed
+        // above: every chain draws its particle at its first update)
+        HIPCHK(e, h.sigma.alloc(K * DP));
+        HIPCHK(e, h.accept.alloc(K * DP));
+        HIPCHK(e, h.hmc.alloc(K * 2));
+        HIPCHK(e, h.sigma.zero(K * DP));
+        HIPCHK(e, h.accept.zero(K * DP));
+        HIPCHK(e, h.hmc.zero(K * 2));
       } else if (h.spec.form == MMB_BINARY_K_LISTS) {
         HIPCHK(e, h.width.alloc(h.tuning.size()));
         HIPCHK(e, hipMemcpy(h.width, h.tuning.data(), h.tuning.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1496,6 +1517,7 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
       case MMB_SAMPLER_DGS: break;  // no tune state; the masses stay in registers (samplers.h dgs)
       case MMB_SAMPLER_SLICESIMPLEX: break;  // no tune state; the vertex matrix lives in LDS within one update
       case MMB_SAMPLER_BIA: s += 8.0 * h.d * 2 + 4.0; break;  // A, D, iter
+      case MMB_SAMPLER_BHMC: s += 8.0 * h.d * 2 + 8.0 * 2 + 4.0; break;  // position, velocity, the counters, initialised
       case MMB_SAMPLER_BMG:
       case MMB_SAMPLER_BMC3: break;  // no tune state
       default: break;
@@ -1534,7 +1556,7 @@ int mmb_amwg_stats(mmb_engine* e, int64_t* out) {
 }
 
 // out[b * width + i]: the first `width` words of block b's astat rows summed over the chains, for the
-// blocks of sampler `kind` (RWM: and the BMG, BMC3 and BIA blocks, which count updates and accepts alike)
+// blocks of sampler `kind` (RWM: and the BMG, BMC3, BIA and BHMC blocks, which count updates and accepts alike)
 static int astat_sums(mmb_engine* e, int kind, int width, int64_t* out) {
   if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
   for (int i = 0; i < MMB_MAX_BLOCKS * width; ++i) out[i] = 0;

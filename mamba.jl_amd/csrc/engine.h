@@ -45,7 +45,7 @@ struct BlockChainBufs {
   DevBuf<double> xnext;    // AMM carried next proposal [K][DP] (samplers.h amm)
   DevBuf<int64_t> xtag;    // AMM [K] tag of the carried proposal
   DevBuf<uint64_t> astat;  // AMM [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats);
-                           // RWM, BMG, BMC3, BIA: the same rows, [0] updates, [1] accepts (mmb_rwm_stats)
+                           // RWM, BMG, BMC3, BIA, BHMC: the same rows, [0] updates, [1] accepts (mmb_rwm_stats)
 };
 
 struct BlockHost : BlockChainBufs {
@@ -187,12 +187,12 @@ static inline bool ir_dgs_family(int fam) {
          fam == MMB_IR_DISCRETEUNIFORM;
 }
 
-// the binary samplers (bmg.jl, bmc3.jl, bia.jl) and the nodes they may sample: Bernoulli, DiscreteUniform(0, 1)
+// the binary samplers (bmg.jl, bmc3.jl, bia.jl, bhmc.jl) and the nodes they may sample: Bernoulli, DiscreteUniform(0, 1)
 static inline bool binary_kind(int kind) {
-  return kind == MMB_SAMPLER_BMG || kind == MMB_SAMPLER_BMC3 || kind == MMB_SAMPLER_BIA;
+  return kind == MMB_SAMPLER_BMG || kind == MMB_SAMPLER_BMC3 || kind == MMB_SAMPLER_BIA || kind == MMB_SAMPLER_BHMC;
 }
 static inline const char* binary_name(int kind) {
-  return kind == MMB_SAMPLER_BMG ? "BMG" : kind == MMB_SAMPLER_BMC3 ? "BMC3" : "BIA";
+  return kind == MMB_SAMPLER_BMG ? "BMG" : kind == MMB_SAMPLER_BMC3 ? "BMC3" : kind == MMB_SAMPLER_BIA ? "BIA" : "BHMC";
 }
 static inline bool ir_binary_node(const mmb_ir_node& n) {
   return n.family == MMB_IR_BERNOULLI || (n.family == MMB_IR_DISCRETEUNIFORM && n.lo == 0.0 && n.hi == 1.0);

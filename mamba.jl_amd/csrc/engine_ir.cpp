@@ -232,7 +232,7 @@ static int ir_validate(const mmb_model_spec* spec, const mmb_ir_model* ir) {
     if (N.family == MMB_IR_POISSON && !N.fixed)  // (infinite support: no DGS)
       return fail(nullptr, MMB_E_UNSUPPORTED, "node IR: Poisson node %d must be fixed (observed)", n);
     const bool dgs = !N.fixed && ir_dgs_family(N.family);
-    if (dgs) {  // a sampled discrete node: in DGS blocks or, a binary one, in BMG, BMC3 or BIA blocks, one node
+    if (dgs) {  // a sampled discrete node: in DGS blocks or, a binary one, in BMG, BMC3, BIA or BHMC blocks, one node
                 // each (create_impl), never another kind
       bool in_dgs = false;
       for (int b = 0; b < spec->nblocks; ++b)
@@ -416,6 +416,8 @@ static const char* const kJitNoBmc3 = "the specialised kernel declines schemes w
                                       "are not generated";
 static const char* const kJitNoBia = "the specialised kernel declines schemes with BIA blocks: the binary samplers "
                                      "are not generated";
+static const char* const kJitNoBhmc = "the specialised kernel declines schemes with BHMC blocks: the binary samplers "
+                                      "are not generated";
 static const char* const kJitNoSimplex = "the specialised kernel declines schemes with SliceSimplex blocks and "
                                          "models with a Dirichlet node or a Categorical that reads a sampled P: "
                                          "they are not generated";
@@ -424,6 +426,7 @@ static const char* ir_jit_declined(unsigned kinds, const mmb_ir_model* ir) {
   if (kinds & (1u << MMB_SAMPLER_BMG)) return kJitNoBmg;
   if (kinds & (1u << MMB_SAMPLER_BMC3)) return kJitNoBmc3;
   if (kinds & (1u << MMB_SAMPLER_BIA)) return kJitNoBia;
+  if (kinds & (1u << MMB_SAMPLER_BHMC)) return kJitNoBhmc;
   if (kinds & (1u << MMB_SAMPLER_SLICESIMPLEX)) return kJitNoSimplex;
   for (int n = 0; n < ir->nnodes; ++n)
     if (ir->nodes[n].family == MMB_IR_DIRICHLET || mmb_ir_cat_state(ir->nodes[n].family, ir->nodes[n].cterm) >= 0)

@@ -15,6 +15,8 @@ int tune_len_of(int kind, int d) {
     case MMB_SAMPLER_BMG: return 0;           // none (BMGTune: logf and the constant k, bmg.jl:7-16)
     case MMB_SAMPLER_BMC3: return 0;          // none (BMC3Tune likewise, bmc3.jl:7-16)
     case MMB_SAMPLER_BIA: return 1 + 2 * d;   // [iter, A[d], D[d]]  (BIATune, bia.jl:5-25)
+    case MMB_SAMPLER_BHMC: return 2 * d + 3;  // [position[d], velocity[d], wallhits, wallcrosses, initialised]
+                                              // (BHMCTune, bhmc.jl:5-19)
     default: return 0;
   }
 }
@@ -138,6 +140,17 @@ int mmb_get_tune(mmb_engine* e, double* tune) {
         t[0] = m[k];
         for (int i = 0; i < h.d; ++i) { t[1 + i] = ta[k * DP + i]; t[1 + h.d + i] = td[k * DP + i]; }
       }
+    } else if (h.spec.sampler == MMB_SAMPLER_BHMC) {
+      std::vector<double> tp, tv, tc;
+      if ((rc = d2h(e, tp, h.sigma, K * DP)) || (rc = d2h(e, tv, h.accept, K * DP)) || (rc = d2h(e, tc, h.hmc, K * 2)))
+        return rc;
+      for (int64_t k = 0; k < K; ++k) {
+        double* t = tune + k * TL + off;
+        for (int i = 0; i < h.d; ++i) { t[i] = tp[k * DP + i]; t[h.d + i] = tv[k * DP + i]; }
+        t[2 * h.d] = tc[k * 2];
+        t[2 * h.d + 1] = tc[k * 2 + 1];
+        t[2 * h.d + 2] = m[k] != 0 ? 1.0 : 0.0;
+      }
     }
     off += h.tune_len;
   }
@@ -162,6 +175,17 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
         if (!ok)
           return fail(e, MMB_E_ARG, "block %d chain %lld: a BIA tune row is [iter, A, D] with iter >= 0 and A, D in "
                       "(epsilon, 1 - epsilon)", (int)b + 1, (long long)k);
+      }
+      continue;
+    }
+    if (h.spec.sampler == MMB_SAMPLER_BHMC) {  // the counters are whole numbers a double holds exactly
+      for (int64_t k = 0; k < K; ++k) {
+        const double* t = tune + k * TL + off + 2 * h.d;
+        bool ok = t[2] == 0.0 || t[2] == 1.0;
+        for (int i = 0; i < 2; ++i) ok = ok && t[i] >= 0.0 && t[i] < 9007199254740992.0 && t[i] == std::floor(t[i]);
+        if (!ok)
+          return fail(e, MMB_E_ARG, "block %d chain %lld: a BHMC tune row is [position, velocity, wallhits, wallcrosses, "
+                      "initialised] with whole counters >= 0 and initialised 0 or 1", (int)b + 1, (long long)k);
       }
       continue;
     }
@@ -255,6 +279,16 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
         for (int i = 0; i < h.d; ++i) { ta[k * DP + i] = t[1 + i]; td[k * DP + i] = t[1 + h.d + i]; }
       }
       if ((rc = h2d(e, h.sigma, ta)) || (rc = h2d(e, h.accept, td))) return rc;
+    } else if (h.spec.sampler == MMB_SAMPLER_BHMC) {
+      std::vector<double> tp(K * DP, 0.0), tv(K * DP, 0.0), tc(K * 2, 0.0);
+      for (int64_t k = 0; k < K; ++k) {
+        const double* t = tune + k * TL + off;
+        for (int i = 0; i < h.d; ++i) { tp[k * DP + i] = t[i]; tv[k * DP + i] = t[h.d + i]; }
+        tc[k * 2] = t[2 * h.d];
+        tc[k * 2 + 1] = t[2 * h.d + 1];
+        m[k] = t[2 * h.d + 2] != 0.0 ? 1 : 0;
+      }
+      if ((rc = h2d(e, h.sigma, tp)) || (rc = h2d(e, h.accept, tv)) || (rc = h2d(e, h.hmc, tc))) return rc;
     }
     if ((rc = h2d(e, h.m, m)) || (rc = h2d(e, h.flags, fl))) return rc;
     off += h.tune_len;

@@ -40,7 +40,7 @@
 #define MMB_SUB_UNIFORM 1u  /* accept / slice / tree uniforms (running index) */
 #define MMB_SUB_GAMMA_N 2u  /* Marsaglia-Tsang normals */
 #define MMB_SUB_GAMMA_U 3u  /* Marsaglia-Tsang uniforms */
-#define MMB_SUB_INIT 4u     /* nutsepsilon momentum (nuts.jl:194) */
+#define MMB_SUB_INIT 4u     /* nutsepsilon momentum (nuts.jl:194); BHMC's first particle: position #i, velocity #(32 + i) */
 #define MMB_SUB_PROPOSAL 5u /* RWM's non-Normal proposal variates (symdist.h): uniform #(8k + j) for coordinate k */
 #define MMB_SUB_SIMPLEX 6u  /* SliceSimplex's Dirichlet(1, ..., 1) draws: uniform #(32r + j) for element j of draw r */
 #define MMB_SUB_BINARY 7u   /* BMG / BMC3: the index set's uniforms #j; BIA: the proposal uniform #j of element j */

@@ -496,6 +496,123 @@ struct Smp {
     M::relist(B, s, g, v);
   }
 
+  // ---------------------------------------------------------------- BHMC
+  // Binary Hamiltonian Monte Carlo (bhmc.jl:50-122) of the block's one Bernoulli or DiscreteUniform(0, 1)
+  // node of n = B.d <= 32 elements, element i on lane i.  The sampler's state is a particle: lane i keeps
+  // position_i, velocity_i and the side S_i of its wall (as x_i = 1 for S_i = +1, 0 for -1) in registers
+  // for the whole update; the per-element arithmetic is bhmc.h's.  Tune per chain: position (B.t_sigma),
+  // velocity (B.t_accept), wallhits and wallcrosses (B.t_hmc, doubles: exact to 2^53, so they do not wrap
+  // at 2^31), initialised (B.t_m).  traveltime = B.scale, refresh = B.form.
+  //
+  // A chain that is not initialised draws its particle first: position_i = normal #i, velocity_i = normal
+  // #(32 + i) of ri, the block's MMB_SUB_INIT stream (the reference's randn(n) when the tune is built,
+  // bhmc.jl:17).  With refresh, velocity_i = normal #i of rn, the block's MMB_SUB_NORMAL stream, at the
+  // start of every update (an extension: the reference never redraws it).  The sides come from the
+  // position (bhmc.jl:58), not from the node's value; S_i = -1 for position_i <= 0.
+  //
+  // One wall event: the walltimes lane-parallel, the last-hit guard on lane j, a (min, lowest index)
+  // reduction over the chain's 32 lanes (lanes >= n hold +Inf), one mmb_sincos of the move time, the move
+  // lane-parallel, and on lane j the bounce.  Of the two configurations at a wall one is the current S,
+  // whose logf is carried: one evaluation of logf at the start and one per event (the reference: two per
+  // event; the same values, logf being a deterministic function of the state).  logf itself is evaluated
+  // by all 32 lanes.  The two chains of a wave run their own event counts, and every cross-lane step (the
+  // DPP stages of the reduction, the 32-wide shuffles, the ballot of grp_any, the DPP sums inside logf)
+  // stays within the chain's own 32 lanes.
+  //
+  // The loop ends by construction: an element hits its wall once per pi of time, so an update has at most
+  // n (floor(traveltime / pi) + 1) events, and the loop makes at most cap = n (floor(traveltime / pi) + 2)
+  // trips, the last of which has to be the final partial move.  A stall -- a zero move time (the
+  // reference's error), a NaN among the walltimes, or cap trips without reaching traveltime -- ends the
+  // update with the node's value and the whole tune row as they were before it.  Updates are counted as
+  // RWM's, an accept being an update that ran to traveltime (mmb_rwm_stats).
+  template <int S_>
+  __device__ __forceinline__ static void bhmc_amin_stage(double& key, int& idx) {
+    const double ok = Grp<G>::template other_d<S_>(key);
+    const int oi = Grp<G>::template other_i<S_>(idx);
+    const bool take = (ok < key) || (ok == key && oi < idx);
+    key = take ? ok : key;
+    idx = take ? oi : idx;
+  }
+  __device__ static void bhmc(const SweepArgs& A, const DBlock& B, int c, const mmb_rng& rn, const mmb_rng& ri, St& s,
+                              const Lc& l, const Grp<G>& g) {
+    static_assert(G == 32 && R == 1, "the binary samplers keep one element per lane of a 32-lane group");
+    const int n = B.d < 32 ? B.d : 32;
+    const bool in = g.lane < n;
+    const size_t at = (size_t)c * DP + (size_t)g.lane;
+    const double T = B.scale;
+    double v[R], x[R];
+    M::unlist(B, s, g.lane, v);
+    double pos, vel;
+    if (B.t_m[c] == 0) {
+      pos = mmb_normal(&ri, (uint32_t)g.lane);
+      vel = mmb_normal(&ri, 32u + (uint32_t)g.lane);
+    } else {
+      pos = in ? B.t_sigma[at] : 0.0;
+      vel = in ? B.t_accept[at] : 0.0;
+    }
+    if (B.form != 0) vel = mmb_normal(&rn, (uint32_t)g.lane);
+    x[0] = (in && pos > 0.0) ? 1.0 : 0.0;
+    double lf = M::logf(A, B, s, l, g, x);
+    const int cap = n * ((int)floor(T / MMB_BHMC_PI) + 2);
+    double total = 0.0;
+    int j = -1, hits = 0, crosses = 0;
+    bool done = false;
+#pragma unroll 1
+    for (int ev = 0; ev < cap; ++ev) {
+      double wt = mmb_bhmc_walltime(vel, pos);
+      if (g.lane == j) wt = mmb_bhmc_guard(wt);
+      wt = in ? wt : __builtin_inf();
+      if (grp_any(wt != wt)) break;
+      double mt = wt;
+      int jj = g.lane;
+      bhmc_amin_stage<0>(mt, jj); bhmc_amin_stage<1>(mt, jj); bhmc_amin_stage<2>(mt, jj);
+      bhmc_amin_stage<3>(mt, jj); bhmc_amin_stage<4>(mt, jj);
+      if (mt == 0.0) break;
+      j = jj;
+      if (mt == __builtin_inf()) mt = MMB_BHMC_PI;
+      total = total + mt;
+      const bool last = total >= T;
+      if (last) mt = mt - (total - T);
+      double sn, cs, a1, b1;
+      mmb_sincos(mt, &sn, &cs);
+      mmb_bhmc_move(vel, pos, sn, cs, &a1, &b1);
+      vel = a1;
+      pos = b1;
+      if (last) {
+        done = true;
+        break;
+      }
+      ++hits;
+      if (g.lane == j) pos = 0.0;
+      double y[R];
+      y[0] = g.lane == j ? 1.0 - x[0] : x[0];
+      const double lo = M::logf(A, B, s, l, g, y);
+      const double xj = __shfl(x[0], j, 32), vj = __shfl(vel, j, 32);
+      int crossed;
+      const double vn = mmb_bhmc_bounce(vj, xj == 1.0 ? lf - lo : lo - lf, &crossed);
+      if (g.lane == j) vel = vn;
+      if (crossed) {
+        x[0] = y[0];
+        lf = lo;
+        ++crosses;
+      }
+    }
+    if (done) {
+      if (in) {
+        B.t_sigma[at] = pos;
+        B.t_accept[at] = vel;
+        v[0] = pos > 0.0 ? 1.0 : 0.0;
+      }
+      if (g.lane == 0) {
+        B.t_m[c] = 1;
+        B.t_hmc[2 * (size_t)c] = B.t_hmc[2 * (size_t)c] + (double)hits;
+        B.t_hmc[2 * (size_t)c + 1] = B.t_hmc[2 * (size_t)c + 1] + (double)crosses;
+      }
+    }
+    bin_count(B, c, done, g);
+    M::relist(B, s, g, v);
+  }
+
   // ---------------------------------------------------------------- SliceSimplex
   // slicesimplex.jl:86-122 (sample!, makefirstsimplex, shrinksimplex) for the block's one Dirichlet node
   // of k = B.d <= 32 elements (node-IR models; M::ssx_* in ir.h), the reference's linear solves

@@ -172,6 +172,12 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
             else S::bia(A, B, c, ru, rb, s, l, g);
           }
           break;
+        case MMB_SAMPLER_BHMC:
+          if constexpr ((KINDS >> MMB_SAMPLER_BHMC) & 1u) {
+            const mmb_rng ri = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_INIT);
+            S::bhmc(A, B, c, rn, ri, s, l, g);
+          }
+          break;
         case MMB_SAMPLER_GIBBS: if constexpr ((KINDS >> MMB_SAMPLER_GIBBS) & 1u) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
           const mmb_rng gu = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_U);
@@ -243,4 +249,6 @@ constexpr unsigned K_DGS = 1u << MMB_SAMPLER_DGS;
 constexpr unsigned K_SIMPLEX = 1u << MMB_SAMPLER_SLICESIMPLEX;
 // The binary samplers BMG, BMC3 and BIA likewise: one instantiation for the three, which holds every other kind
 constexpr unsigned K_BIN = (1u << MMB_SAMPLER_BMG) | (1u << MMB_SAMPLER_BMC3) | (1u << MMB_SAMPLER_BIA);
+// BHMC likewise: one further instantiation, which holds every other kind
+constexpr unsigned K_BHMC = 1u << MMB_SAMPLER_BHMC;
 

@@ -26,7 +26,7 @@ DiscreteUniform for fixed nodes; + - * / neg abs exp log sqrt invlogit logit, x*
 <= 32 elements.
 
 Binary nodes (src/samplers/bmg.jl, bmc3.jl, bia.jl): a Bernoulli or DiscreteUniform(0, 1) node of at most 32
-elements may instead be sampled by one `BMG`, `BMC3` or `BIA` block, which holds that node alone.
+elements may instead be sampled by one `BMG`, `BMC3`, `BIA` or `BHMC` (bhmc.jl) block, which holds that node alone.
 
 Discrete nodes (src/samplers/dgs.jl): a Bernoulli, Binomial (n data), Categorical(p) (p a constant
 list or a data vector shared by every element, support 1..K) or DiscreteUniform(a, b) (constant
@@ -424,7 +424,7 @@ class Model(_BaseModel):
                 raise ArgumentError(f"incompatible initial value for node : {n}")
             self.lens[n] = v.size
         self.fixed_vals = {n: self._initval(init0, n) for n in self.fixed}
-        binary = (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA)
+        binary = (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA, abi.MMB_SAMPLER_BHMC)
         by_dgs = {p for s in self.samplers if s.kind == abi.MMB_SAMPLER_DGS or s.kind in binary for p in s.params}
         for s in self.samplers:
             for n in s.params:

@@ -173,15 +173,30 @@ class Engine:
 
     def accept_stats(self):
         """Update and accept counters since init_chains of every block that has a Metropolis accept step
-        and counts it (mmb_rwm_stats): RWM, BMG, BMC3 and BIA blocks, one dict per block keyed by block
+        and counts it (mmb_rwm_stats): RWM, BMG, BMC3, BIA and BHMC blocks, one dict per block keyed by block
         index, summed over the chains.  A BMG block of one element has no accept step (bmg.jl:83-84):
-        every update counts as accepted."""
-        kinds = (abi.MMB_SAMPLER_RWM, abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA)
+        every update counts as accepted.  A BHMC block's accepts are the updates that ran to traveltime:
+        updates - accepts of them stalled and left the chain as it was."""
+        kinds = (abi.MMB_SAMPLER_RWM, abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA,
+                 abi.MMB_SAMPLER_BHMC)
         v = (C.c_int64 * (abi.MMB_MAX_BLOCKS * 2))()
         self._chk(self.lib.mmb_rwm_stats(self.h, v))
         return {b: {"updates": v[2 * b], "accepts": v[2 * b + 1],
                     "rate": v[2 * b + 1] / v[2 * b] if v[2 * b] else float("nan")}
                 for b, blk in enumerate(self.model.samplers) if getattr(blk, "kind", None) in kinds}
+
+    def bhmc_stats(self):
+        """Per BHMC block (keyed by block index): `wallhits` and `wallcrosses` (BHMCTune, bhmc.jl:10-11), one
+        entry per chain, since the chain's particle was drawn; read from the tune rows."""
+        t = self.tune()
+        out, off = {}, 0
+        for b, blk in enumerate(self.model.samplers):
+            d = self.model.block_dim(blk)
+            if blk.kind == abi.MMB_SAMPLER_BHMC:
+                out[b] = {"wallhits": t[:, off + 2 * d].astype(np.int64),
+                          "wallcrosses": t[:, off + 2 * d + 1].astype(np.int64)}
+            off += blk.tune_len(d)
+        return out
 
     def amwg_stats(self):
         """AMWG block updates since init_chains that ran the sequential coordinate loop

@@ -48,7 +48,7 @@ class Model:
         for s in samplers:
             if s.kind == abi.MMB_SAMPLER_DGS:
                 raise ArgumentError("DGS samples the discrete nodes of node-IR models (ir.Model) only")
-            if s.kind in (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA):
+            if s.kind in (abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA, abi.MMB_SAMPLER_BHMC):
                 raise ArgumentError(f"{s!r} samples the binary nodes of node-IR models (ir.Model) only")
             if s.kind == abi.MMB_SAMPLER_SLICESIMPLEX:
                 raise ArgumentError("SliceSimplex samples the Dirichlet nodes of node-IR models (ir.Model) only")

@@ -19,9 +19,13 @@ Argument meaning, defaults and validation errors follow the reference:
                   node (node-IR models; no tuning)            src/samplers/bmg.jl:42-50, bmc3.jl:42-50
   BIA(params, A, D, epsilon, decay=0.55, target=0.45)  -- binary individual adaptation; A and D
                   always adapt (node-IR models)               src/samplers/bia.jl:18-24, bia.jl:55-63
+  BHMC(params, traveltime, refresh=False)  -- binary Hamiltonian Monte Carlo on one Bernoulli node
+                  (node-IR models; the particle is the tune state)      src/samplers/bhmc.jl:35-43
   Gibbs(params)  -- a user `Sampler(params, f)` whose f is the node's conjugate full
                     conditional (doc/tutorial/line.jl:27-45); lowered per model.
 """
+import math
+
 import numpy as np
 
 from . import abi
@@ -110,6 +114,12 @@ class Sampler:
                 raise ArgumentError("target is not in (0, 1)")
             self.epsilon = eps
             self.tuning = np.concatenate([a, dd])
+        if self.kind == abi.MMB_SAMPLER_BHMC:
+            if not 1 <= dim <= abi.MMB_BINARY_MAX:
+                raise ArgumentError(f"a BHMC block holds a node of 1..{abi.MMB_BINARY_MAX} elements")
+            # an update has at most dim (floor(traveltime / pi) + 2) wall events: the cap keeps that bounded
+            if not (math.isfinite(self.scale) and 0.0 < self.scale <= abi.MMB_BHMC_MAX_TRAVELTIME):
+                raise ArgumentError("traveltime is not finite, > 0 and <= 128 pi")
 
     def spec_tuning(self, dim):
         """`tuning` as the block spec carries it: RWM's scalar scale is broadcast to the variate length
@@ -118,13 +128,21 @@ class Sampler:
             return np.full(dim, self.tuning[0])
         return self.tuning
 
+    def tune_len(self, dim):
+        """Length of the block's canonical tune row (csrc/engine_tune.cpp tune_len_of) for a variate of
+        `dim` elements."""
+        tri = dim * (dim + 1) // 2
+        return {abi.MMB_SAMPLER_AMWG: 2 + 2 * dim, abi.MMB_SAMPLER_AMM: 4 + 2 * dim + 2 * tri, abi.MMB_SAMPLER_NUTS: 9,
+                abi.MMB_SAMPLER_HMC: 2, abi.MMB_SAMPLER_MALA: 1, abi.MMB_SAMPLER_RWM: dim,
+                abi.MMB_SAMPLER_BIA: 1 + 2 * dim, abi.MMB_SAMPLER_BHMC: 2 * dim + 3}.get(self.kind, 0)
+
     def __repr__(self):
         return f"{self.name}({self.params})"
 
     @property
     def name(self):
         return {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS",
-                10: "SliceSimplex", 11: "BMG", 12: "BMC3", 13: "BIA"}[self.kind]
+                10: "SliceSimplex", 11: "BMG", 12: "BMC3", 13: "BIA", 14: "BHMC"}[self.kind]
 
 
 def AMWG(params, sigma, adapt="all", batchsize=50, target=0.44):
@@ -290,6 +308,31 @@ def BIA(params, A=None, D=None, epsilon=None, decay=0.55, target=0.45):
     except (TypeError, ValueError):
         raise ArgumentError("decay and target are numbers") from None
     s.bia = (A, D, epsilon)
+    return s
+
+
+def BHMC(params, traveltime, refresh=False):
+    """BHMC(params, traveltime) -- bhmc.jl:35-43: binary Hamiltonian Monte Carlo on the one Bernoulli (or
+    DiscreteUniform(0, 1)) node of `params`, 1..32 elements.  The sampler's state is a particle (position and
+    velocity per element), drawn once at the chain's first update and moved on from where the last update left
+    it; the node's value is the side of each element's wall.  `traveltime` is finite, > 0 and at most 128 pi
+    (the cap bounds an update's wall events; checked once the node's length is known).  refresh=False is the
+    reference, which never redraws the velocity and so does not target the exact posterior; refresh=True (an
+    extension: Pakman & Paninski's algorithm) redraws it at the start of every update.  Tune row
+    [position[n], velocity[n], wallhits, wallcrosses, initialised].  Node-IR models only."""
+    params = _params(params)
+    if len(params) != 1:
+        raise ArgumentError(f"BHMC({params}) is one joint move over all the listed nodes in the reference, which a "
+                            "block of one node cannot restate: give BHMC one node")
+    if isinstance(refresh, (bool, np.bool_)):
+        refresh = bool(refresh)
+    else:
+        raise ArgumentError("refresh is True or False")
+    try:
+        s = Sampler(params, abi.MMB_SAMPLER_BHMC, abi.MMB_ADAPT_NONE, None, form=int(refresh), scale=traveltime)
+    except (TypeError, ValueError):
+        raise ArgumentError("traveltime is a number") from None
+    s.traveltime, s.refresh = s.scale, refresh
     return s
 
 
