@@ -103,8 +103,32 @@ typedef enum {
    * <= MMB_BHMC_MAX_TRAVELTIME; refresh in form (0: the reference, the velocity is never redrawn; 1: it is
    * redrawn at the start of every update).  Tune row [position[dim], velocity[dim], wallhits, wallcrosses,
    * initialised]; a chain whose `initialised` is 0 draws its particle at its first update. */
-  MMB_SAMPLER_BHMC = 14  /* src/samplers/bhmc.jl:35-122: binary Hamiltonian Monte Carlo */
+  MMB_SAMPLER_BHMC = 14, /* src/samplers/bhmc.jl:35-122: binary Hamiltonian Monte Carlo */
+  /* ABC of one or more continuous node-IR nodes (additive too; node-IR models only).  Packed into the fields of
+   * mmb_block_spec:
+   *   form       proposal | kernel << 8 | randeps << 16   (proposal, kernel: mmb_rwm_proposal; randeps 0 or 1)
+   *   batchsize  maxdraw, 1..MMB_ABC_MAX_DRAW          nsteps   nsim, 1..MMB_ABC_MAX_NSIM
+   *   beta       decay in [0, 1]                       epsilon  the target tolerance, finite and > 0
+   *   transform  1                                     tuning   scale[dim] (finite, >= 0), then the summary codes
+   *                                                             (mmb_abc_summary, 1..MMB_ABC_MAX_SUMMARY of them)
+   * The data nodes are the block's terms that are not its params (mmb_ir_block.term with trans == 0), in term
+   * order: at least one, at most MMB_ABC_MAX_DATA, each a Normal, MvNormal, Bernoulli, Binomial, Poisson,
+   * Exponential or Uniform node.  Each contributes its summary (the listed statistics in the listed order;
+   * MMB_ABC_IDENTITY, which may only stand alone: its elements) and the summaries are concatenated: T = their
+   * total length, 1..MMB_ABC_MAX_T.  MMB_ABC_VAR and MMB_ABC_STD need nodes of >= 2 elements.
+   * Tune row [initialised, Tsim[nsim][T], epsilon[nsim], epsilonprime[nsim]], length 1 + nsim (T + 2); a chain
+   * whose `initialised` is 0 simulates its first Tsim at its first update (abc.jl:47-83). */
+  MMB_SAMPLER_ABC = 15   /* src/samplers/abc.jl:23-147: approximate Bayesian computation */
 } mmb_sampler_kind;
+typedef enum {
+  MMB_ABC_IDENTITY = 0, MMB_ABC_SUM = 1, MMB_ABC_MEAN = 2, MMB_ABC_VAR = 3, MMB_ABC_STD = 4, MMB_ABC_MINIMUM = 5,
+  MMB_ABC_MAXIMUM = 6
+} mmb_abc_summary;
+#define MMB_ABC_MAX_DRAW 1024
+#define MMB_ABC_MAX_NSIM 8
+#define MMB_ABC_MAX_T 32
+#define MMB_ABC_MAX_DATA 16
+#define MMB_ABC_MAX_SUMMARY 8
 typedef enum { MMB_BINARY_K_INT = 0, MMB_BINARY_K_LISTS = 1 } mmb_binary_form;
 #define MMB_BINARY_MAX_LISTS 64
 #define MMB_BINARY_MAX 32
@@ -139,19 +163,21 @@ typedef struct {
   int32_t nodes[MMB_MAX_NODES_PER_BLOCK];  /* node ids in block (params) order */
   int32_t adapt;                           /* AMWG/AMM: mmb_adapt (default :all) */
   int32_t form;                            /* Slice: mmb_slice_form (default Multivariate); RWM: mmb_rwm_proposal;
-                                              BMG/BMC3: mmb_binary_form; BHMC: refresh (0 or 1) */
+                                              BMG/BMC3: mmb_binary_form; BHMC: refresh (0 or 1);
+                                              ABC: proposal | kernel << 8 | randeps << 16 */
   int32_t transform;                       /* Slice: transform flag (default false); AMWG/AMM/NUTS/RWM use true */
-  int32_t batchsize;                       /* AMWG batchsize (default 50) */
+  int32_t batchsize;                       /* AMWG batchsize (default 50); ABC maxdraw */
   double target;                           /* AMWG target (0.44) / NUTS target (0.6) / BIA target (0.45) */
-  double beta;                             /* AMM beta (0.05); BIA decay (0.55) */
+  double beta;                             /* AMM beta (0.05); BIA decay (0.55); ABC decay (1.0) */
   double scale;                            /* AMM scale (2.38); SliceSimplex scale in (0, 1]; BHMC traveltime */
   int32_t dim;                             /* unlisted block length (checked by mmb_create) */
   int32_t ntuning;                         /* length of `tuning` */
   const double* tuning;                    /* AMWG sigma[dim] | Slice width[dim] | RWM scale[dim] | AMM Sigma[dim*dim] col-major
                                               | HMC/MALA Sigma[dim*dim] col-major, or none (SigmaL = I)
-                                              | BMG/BMC3 list masks | BIA A[dim], D[dim] */
-  double epsilon;                          /* HMC/MALA step size (hmc.jl:13, mala.jl:12); BIA epsilon (bia.jl:21) */
-  int32_t nsteps;                          /* HMC leapfrog steps L (hmc.jl:13); BMG/BMC3 int k */
+                                              | BMG/BMC3 list masks | BIA A[dim], D[dim]
+                                              | ABC scale[dim], summary codes */
+  double epsilon;                          /* HMC/MALA step size (hmc.jl:13, mala.jl:12); BIA epsilon (bia.jl:21); ABC epsilon */
+  int32_t nsteps;                          /* HMC leapfrog steps L (hmc.jl:13); BMG/BMC3 int k; ABC nsim */
   int32_t gradient;                        /* NUTS/HMC/MALA logpdfgrad! (sampler.jl:97-111): mmb_gradient */
 } mmb_block_spec;
 
@@ -639,7 +665,8 @@ int mmb_amwg_stats(mmb_engine* e, int64_t* out /* 1 */);
  * A user sizes `scale` from this acceptance rate (RWM does not adapt).  BMG, BMC3 and BIA blocks fill
  * their rows the same way (a BMG block of one element has no accept step: every update counts as
  * accepted), and so do BHMC blocks, whose accepts are the updates that ran to traveltime (the others
- * stalled and changed nothing).  Diagnostics only. */
+ * stalled and changed nothing), and ABC blocks, whose accepts are the updates that took a
+ * candidate.  Diagnostics only. */
 int mmb_rwm_stats(mmb_engine* e, int64_t* out /* MMB_MAX_BLOCKS x 2 */);
 
 /* The lane-group slot -> chain table the next window will run with (K entries; the identity

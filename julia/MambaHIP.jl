@@ -29,6 +29,7 @@ const MMB_SAMPLER_RWM = Int32(8)
 # the binary samplers of node-IR models (bmg.jl, bmc3.jl, bia.jl): ids only, the shim does not register them yet
 const MMB_SAMPLER_BMG, MMB_SAMPLER_BMC3, MMB_SAMPLER_BIA = Int32(11), Int32(12), Int32(13)
 const MMB_SAMPLER_BHMC = Int32(14)  # bhmc.jl: id only, likewise
+const MMB_SAMPLER_ABC = Int32(15)   # abc.jl: id only, likewise
 # mmb_rwm_proposal: Normal and the SymDistributionTypes (src/distributions/extensions.jl:51-53)
 const MMB_RWM_PROPOSAL = Dict{Any,Int32}(Distributions.Normal => 0, Mamba.SymUniform => 1,
                                          Mamba.SymTriangularDist => 2, Mamba.Epanechnikov => 3,

@@ -17,7 +17,7 @@ from .modelstats import dic, dic_sharded, logpdf, logpdf_sharded  # noqa: F401
 from .modelstats import predict, predict_moments_sharded, predict_sharded, predict_summary  # noqa: F401
 from .mcmc import Chains, Engine, mcmc, mcmc_restart, read, write  # noqa: F401
 from .model import line, logistic, rats  # noqa: F401
-from .samplers import (AMM, AMWG, BHMC, BIA, BMC3, BMG, DGS, HMC, MALA, NUTS, RWM, ArgumentError, Gibbs, Multivariate, Sampler,  # noqa: F401
+from .samplers import (ABC, AMM, AMWG, BHMC, BIA, BMC3, BMG, DGS, HMC, MALA, NUTS, RWM, ArgumentError, Gibbs, Multivariate, Sampler,  # noqa: F401
                        Slice, SliceSimplex, Univariate)
 from .samplers import (Biweight, Cosine, Epanechnikov, Normal, SymTriangularDist, SymUniform,  # noqa: F401
                        Triweight)

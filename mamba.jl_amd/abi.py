@@ -26,6 +26,11 @@ MMB_BINARY_MAX_LISTS, MMB_BINARY_MAX = 64, 32
 MMB_SAMPLER_BHMC = 14  # binary Hamiltonian Monte Carlo: additive too
 MMB_BHMC_MAX_TRAVELTIME = 402.1238596594935  # 128 pi: bounds an update's wall events
 MMB_SUB_NORMAL, MMB_SUB_INIT = 0, 4  # csrc/mmb_math.h: BHMC's refreshed velocities / its first particle
+MMB_SAMPLER_ABC = 15  # approximate Bayesian computation: additive too
+MMB_ABC_MAX_DRAW, MMB_ABC_MAX_NSIM, MMB_ABC_MAX_T, MMB_ABC_MAX_DATA, MMB_ABC_MAX_SUMMARY = 1024, 8, 32, 16, 8
+(MMB_ABC_IDENTITY, MMB_ABC_SUM, MMB_ABC_MEAN, MMB_ABC_VAR, MMB_ABC_STD, MMB_ABC_MINIMUM,
+ MMB_ABC_MAXIMUM) = range(7)  # mmb_abc_summary
+MMB_SUB_ABC_N, MMB_SUB_ABC_U = 8, 9  # csrc/mmb_math.h: the normals / uniforms of ABC's simulated data
 MMB_SUB_BINARY = 7  # csrc/mmb_math.h: index-set uniforms of BMG / BMC3, proposal uniforms of BIA
 (MMB_RWM_NORMAL, MMB_RWM_SYMUNIFORM, MMB_RWM_SYMTRIANGULAR, MMB_RWM_EPANECHNIKOV, MMB_RWM_BIWEIGHT,
  MMB_RWM_TRIWEIGHT, MMB_RWM_COSINE) = range(7)

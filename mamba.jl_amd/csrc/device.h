@@ -16,6 +16,7 @@
 #include "mmb_math.h"
 #include "symdist.h"
 #include "bhmc.h"
+#include "abc.h"
 #include "ir_math.h"
 
 #define MMB_MAXB MMB_MAX_BLOCKS

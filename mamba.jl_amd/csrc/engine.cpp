@@ -74,6 +74,75 @@ const char* mmb_last_error(const mmb_engine* e) {
   return g_last_error.c_str();
 }
 
+// An ABC block's spec (mamba_hip.h MMB_SAMPLER_ABC) checked against the lowered model, and its device table
+// [T, ns, nd, codes[ns], then per data node (node id, first statistic)] (samplers.h abc).  Returns the reason
+// for a refusal, or null.
+static const char* abc_family_name(int fam) {
+  switch (fam) {
+    case MMB_IR_GAMMA: return "Gamma";
+    case MMB_IR_INVGAMMA: return "InverseGamma";
+    case MMB_IR_BETA: return "Beta";
+    case MMB_IR_CATEGORICAL: return "Categorical";
+    case MMB_IR_DISCRETEUNIFORM: return "DiscreteUniform";
+    case MMB_IR_DIRICHLET: return "Dirichlet";
+    default: return "this family";
+  }
+}
+static const char* abc_table(const mmb_block_spec& s, const mmb_ir_node* nodes, int nnodes, const mmb_ir_block& IB, int d,
+                             std::vector<int32_t>& tab) {
+  static thread_local char msg[160];
+  const int prop = s.form & 0xff, kern = (s.form >> 8) & 0xff;
+  if (s.form < 0 || (s.form >> 17) != 0 || prop > MMB_RWM_COSINE || kern > MMB_RWM_COSINE)
+    return "ABC form is proposal | kernel << 8 | randeps << 16 with proposal and kernel in 0..6";
+  if (!(s.beta >= 0.0 && s.beta <= 1.0)) return "decay is not in [0, 1]";
+  if (!(std::isfinite(s.epsilon) && s.epsilon > 0.0)) return "epsilon is not finite and > 0";
+  if (s.batchsize < 1 || s.batchsize > MMB_ABC_MAX_DRAW) return "maxdraw is not in 1..1024";
+  if (s.nsteps < 1 || s.nsteps > MMB_ABC_MAX_NSIM) return "nsim is not in 1..8";
+  if (s.transform != 1) return "ABC unlists its nodes with transform (transform = 1)";
+  const int ns = s.ntuning - d;
+  if (s.dim != d || ns < 1 || ns > MMB_ABC_MAX_SUMMARY || !s.tuning)
+    return "ABC tuning is scale[dim] followed by 1..8 summary codes";
+  for (int i = 0; i < d; ++i)
+    if (!(std::isfinite(s.tuning[i]) && s.tuning[i] >= 0.0)) return "ABC scale must be finite and >= 0";
+  bool var = false;
+  for (int q = 0; q < ns; ++q) {
+    const double cd = s.tuning[d + q];
+    if (!(cd >= MMB_ABC_IDENTITY && cd <= MMB_ABC_MAXIMUM) || cd != std::floor(cd)) return "unknown summary code";
+    if (cd == MMB_ABC_IDENTITY && ns != 1) return "the identity summary may only stand alone";
+    var = var || cd == MMB_ABC_VAR || cd == MMB_ABC_STD;
+  }
+  for (int a = 0; a < s.nnodes; ++a)
+    if (ir_dgs_family(nodes[s.nodes[a]].family) || nodes[s.nodes[a]].family == MMB_IR_POISSON)
+      return "ABC samples continuous nodes";
+  tab.assign(3 + ns, 0);
+  for (int q = 0; q < ns; ++q) tab[3 + q] = (int32_t)s.tuning[d + q];
+  const bool ident = tab[3] == MMB_ABC_IDENTITY;
+  int T = 0, nd = 0;
+  for (int t = 0; t < IB.nterms && t < MMB_IR_MAX_TERMS; ++t) {
+    if (IB.trans[t]) continue;
+    const int n = IB.term[t];
+    if (n < 0 || n >= nnodes) return "ABC: a term of the block is not a node";
+    const mmb_ir_node& N = nodes[n];
+    if (!mmb_abc_data_family(N.family)) {
+      snprintf(msg, sizeof msg, "ABC cannot simulate data node %d: %s data nodes are not supported", n,
+               abc_family_name(N.family));
+      return msg;
+    }
+    if (var && N.len < 2) return "the var and std summaries need data nodes of >= 2 elements";
+    if (nd == MMB_ABC_MAX_DATA) return "ABC: at most 16 data nodes";
+    tab.push_back(n);
+    tab.push_back(T);
+    T += ident ? N.len : ns;
+    if (T > MMB_ABC_MAX_T) return "the total summary length is not in 1..32";
+    ++nd;
+  }
+  if (nd < 1) return "ABC needs at least one data node among the block's targets";
+  tab[0] = T;
+  tab[1] = ns;
+  tab[2] = nd;
+  return nullptr;
+}
+
 int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, mmb_engine** out) {
   if (!spec || !out) return fail(nullptr, MMB_E_ARG, "null argument");
   *out = nullptr;
@@ -368,6 +437,15 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
         }
         break;
       }
+      case MMB_SAMPLER_ABC: {  // abc.jl:23-51: the packing is documented at MMB_SAMPLER_ABC (mamba_hip.h)
+        const char* why = e->model != MMB_MODEL_IR ? "ABC samples the nodes of node-IR models only"
+                                                   : abc_table(s, ir->nodes, ir->nnodes, ir->blocks[b], d, h.abc_tab);
+        if (why) {
+          delete e;
+          return fail(nullptr, MMB_E_ARG, "block %d: %s", b, why);
+        }
+        break;
+      }
       default:
         delete e;
         return fail(nullptr, MMB_E_ARG, "unknown sampler kind %d", s.sampler);
@@ -385,7 +463,8 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
           delete e;
           return fail(nullptr, MMB_E_ARG, "block %d: discrete node %d can be sampled by a DGS block only", b, s.nodes[a]);
         }
-    h.tune_len = tune_len_of(s.sampler, d);
+    h.tune_len = s.sampler == MMB_SAMPLER_ABC ? tune_len_of(s.sampler, d, s.nsteps, h.abc_tab[0])
+                                              : tune_len_of(s.sampler, d);
     e->kinds |= 1u << s.sampler;
     e->blocks.push_back(std::move(h));
   }
@@ -433,6 +512,8 @@ int create_impl(const mmb_model_spec* spec, const mmb_ir_model* ir, int device, 
           ir_sep_table(e->ir_nodes, e->ir_code, e->ir_pool, e->ir_blocks[b], h.spec, e->P, tab, &h.sep_eps))
         up(h.sep_d, tab);
     }
+    for (auto& h : e->blocks)
+      if (h.spec.sampler == MMB_SAMPLER_ABC) up(h.sep_d, h.abc_tab);
     if (!ok) {
       mmb_destroy(e);
       return fail(nullptr, MMB_E_HIP, "node IR upload failed");
@@ -677,8 +758,9 @@ static int upload_blocks(mmb_engine* e) {
     d.nn = h.spec.nnodes;
     d.d = h.d;
     d.transform = h.spec.sampler == MMB_SAMPLER_SLICE ? h.spec.transform : binary_kind(h.spec.sampler) ? 0 : 1;
+    const bool abc = h.spec.sampler == MMB_SAMPLER_ABC;
     d.form = h.spec.form;
-    d.adapt = h.spec.adapt;
+    d.adapt = abc ? h.spec.nsteps : h.spec.adapt;  // ABC: nsim (maxdraw in batchsize, samplers.h abc)
     d.batchsize = h.spec.batchsize;
     // BMG / BMC3: the int k, or the number of index lists (their masks: d.width)
     if (h.spec.sampler == MMB_SAMPLER_BMG || h.spec.sampler == MMB_SAMPLER_BMC3)
@@ -700,7 +782,7 @@ static int upload_blocks(mmb_engine* e) {
     }
     d.target = h.spec.target;
     d.beta = h.spec.beta;
-    d.scale = h.spec.sampler == MMB_SAMPLER_BIA ? h.spec.epsilon : h.spec.scale;
+    d.scale = (h.spec.sampler == MMB_SAMPLER_BIA || abc) ? h.spec.epsilon : h.spec.scale;
     d.width0 = h.tuning.empty() ? 0.0 : h.tuning[0];
     d.width = (h.spec.sampler == MMB_SAMPLER_SLICE && h.tuning.size() > 1) ? h.width.get() : nullptr;
     if ((h.spec.sampler == MMB_SAMPLER_BMG || h.spec.sampler == MMB_SAMPLER_BMC3) && h.spec.form == MMB_BINARY_K_LISTS)
@@ -795,6 +877,18 @@ int mmb_init_chains(mmb_engine* e, const double* init, int64_t K, int64_t chain_
       for (int64_t k = 0; k < K; ++k)
         for (int i = 0; i < h.d; ++i) sg[k * DP + i] = h.tuning[i];
       HIPCHK(e, hipMemcpy(h.sigma, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(e, h.astat.alloc(K * MMB_AMM_STAT_STRIDE));
+      HIPCHK(e, h.astat.zero(K * MMB_AMM_STAT_STRIDE));
+    } else if (h.spec.sampler == MMB_SAMPLER_ABC) {
+      // scale in sigma (as RWM's); the canonical tune row in hmc, zeroed: every chain simulates its first Tsim
+      // at its first update
+      HIPCHK(e, h.sigma.alloc(K * DP));
+      std::vector<double> sg(K * DP, 0.0);
+      for (int64_t k = 0; k < K; ++k)
+        for (int i = 0; i < h.d; ++i) sg[k * DP + i] = h.tuning[i];
+      HIPCHK(e, hipMemcpy(h.sigma, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(e, h.hmc.alloc((size_t)K * h.tune_len));
+      HIPCHK(e, h.hmc.zero((size_t)K * h.tune_len));
       HIPCHK(e, h.astat.alloc(K * MMB_AMM_STAT_STRIDE));
       HIPCHK(e, h.astat.zero(K * MMB_AMM_STAT_STRIDE));
     } else if (h.spec.sampler == MMB_SAMPLER_NUTS) {
@@ -1518,6 +1612,7 @@ int mmb_state_bytes(const mmb_engine* e, double* bytes) {
       case MMB_SAMPLER_SLICESIMPLEX: break;  // no tune state; the vertex matrix lives in LDS within one update
       case MMB_SAMPLER_BIA: s += 8.0 * h.d * 2 + 4.0; break;  // A, D, iter
       case MMB_SAMPLER_BHMC: s += 8.0 * h.d * 2 + 8.0 * 2 + 4.0; break;  // position, velocity, the counters, initialised
+      case MMB_SAMPLER_ABC: s += 8.0 * h.d + 8.0 * h.tune_len; break;     // scale, the tune row
       case MMB_SAMPLER_BMG:
       case MMB_SAMPLER_BMC3: break;  // no tune state
       default: break;
@@ -1556,7 +1651,7 @@ int mmb_amwg_stats(mmb_engine* e, int64_t* out) {
 }
 
 // out[b * width + i]: the first `width` words of block b's astat rows summed over the chains, for the
-// blocks of sampler `kind` (RWM: and the BMG, BMC3, BIA and BHMC blocks, which count updates and accepts alike)
+// blocks of sampler `kind` (RWM: and the BMG, BMC3, BIA, BHMC and ABC blocks, which count updates and accepts alike)
 static int astat_sums(mmb_engine* e, int kind, int width, int64_t* out) {
   if (!e || !out) return fail(e, MMB_E_ARG, "null argument");
   for (int i = 0; i < MMB_MAX_BLOCKS * width; ++i) out[i] = 0;
@@ -1566,7 +1661,7 @@ static int astat_sums(mmb_engine* e, int kind, int width, int64_t* out) {
   std::vector<uint64_t> h;
   for (size_t b = 0; b < e->blocks.size(); ++b) {
     const int bk = e->blocks[b].spec.sampler;
-    if (!e->blocks[b].astat || !(bk == kind || (kind == MMB_SAMPLER_RWM && binary_kind(bk)))) continue;
+    if (!e->blocks[b].astat || !(bk == kind || (kind == MMB_SAMPLER_RWM && (binary_kind(bk) || bk == MMB_SAMPLER_ABC)))) continue;
     int rc = d2h(e, h, e->blocks[b].astat, (size_t)e->K * MMB_AMM_STAT_STRIDE);
     if (rc) return rc;
     for (int64_t k = 0; k < e->K; ++k)

@@ -39,13 +39,13 @@ struct BlockChainBufs {
   // current Mv / Mvv are in these when its m is odd.  Null: one buffer
   DevBuf<double> Mv_alt, Mvv_alt;
   DevBuf<double> nuts, nfr, width, sigl_d;
-  DevBuf<double> hmc;  // HMC/MALA [K][2] epsilon, L
+  DevBuf<double> hmc;  // HMC/MALA [K][2] epsilon, L; ABC [K][tune_len] the canonical tune row
   DevBuf<int32_t> m, flags;
   DevBuf<uint8_t> piv;
   DevBuf<double> xnext;    // AMM carried next proposal [K][DP] (samplers.h amm)
   DevBuf<int64_t> xtag;    // AMM [K] tag of the carried proposal
   DevBuf<uint64_t> astat;  // AMM [K][MMB_AMM_STAT_STRIDE] factorization counters (mmb_amm_stats);
-                           // RWM, BMG, BMC3, BIA, BHMC: the same rows, [0] updates, [1] accepts (mmb_rwm_stats)
+                           // RWM, BMG, BMC3, BIA, BHMC, ABC: the same rows, [0] updates, [1] accepts (mmb_rwm_stats)
 };
 
 struct BlockHost : BlockChainBufs {
@@ -54,8 +54,10 @@ struct BlockHost : BlockChainBufs {
   int d = 0, T = 0, tune_len = 0;
   std::vector<double> sigl;  // AMM chol(Sigma) lower row-major
   bool sigl_diag = false;
-  DevBuf<int32_t> sep_d;  // node-IR AMWG: coordinate -> element-term table (ir_sep_table), engine lifetime
+  DevBuf<int32_t> sep_d;  // node-IR AMWG: coordinate -> element-term table (ir_sep_table), engine lifetime;
+                          // ABC: the block's table (abc_tab)
   double sep_eps = 0.0;
+  std::vector<int32_t> abc_tab;  // ABC: [T, ns, nd, codes[ns], then per data node (node id, first statistic)]
 };
 
 // The engine's per-chain device state: dropped as one group like the blocks' (free_dev)
@@ -217,7 +219,7 @@ void ir_fuse(const std::vector<int32_t>& code, std::vector<mmb_ir_node>& nodes,
 int ir_state_len(const mmb_model_spec* spec, const mmb_ir_model* ir);
 
 // engine_tune.cpp
-int tune_len_of(int kind, int d);
+int tune_len_of(int kind, int d, int nsim = 0, int nstat = 0);
 
 // engine_post.cpp
 int gr_width_check(mmb_engine* e);

@@ -418,6 +418,8 @@ static const char* const kJitNoBia = "the specialised kernel declines schemes wi
                                      "are not generated";
 static const char* const kJitNoBhmc = "the specialised kernel declines schemes with BHMC blocks: the binary samplers "
                                       "are not generated";
+static const char* const kJitNoAbc = "the specialised kernel declines schemes with ABC blocks: the ABC update "
+                                     "is not generated";
 static const char* const kJitNoSimplex = "the specialised kernel declines schemes with SliceSimplex blocks and "
                                          "models with a Dirichlet node or a Categorical that reads a sampled P: "
                                          "they are not generated";
@@ -427,6 +429,7 @@ static const char* ir_jit_declined(unsigned kinds, const mmb_ir_model* ir) {
   if (kinds & (1u << MMB_SAMPLER_BMC3)) return kJitNoBmc3;
   if (kinds & (1u << MMB_SAMPLER_BIA)) return kJitNoBia;
   if (kinds & (1u << MMB_SAMPLER_BHMC)) return kJitNoBhmc;
+  if (kinds & (1u << MMB_SAMPLER_ABC)) return kJitNoAbc;
   if (kinds & (1u << MMB_SAMPLER_SLICESIMPLEX)) return kJitNoSimplex;
   for (int n = 0; n < ir->nnodes; ++n)
     if (ir->nodes[n].family == MMB_IR_DIRICHLET || mmb_ir_cat_state(ir->nodes[n].family, ir->nodes[n].cterm) >= 0)

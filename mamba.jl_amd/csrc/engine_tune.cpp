@@ -2,7 +2,7 @@
 // and the device's tune state (mmb_get_tune / mmb_set_tune).
 #include "engine.h"
 
-int tune_len_of(int kind, int d) {
+int tune_len_of(int kind, int d, int nsim, int nstat) {
   switch (kind) {
     case MMB_SAMPLER_AMWG: return 2 + 2 * d;
     case MMB_SAMPLER_AMM: return 4 + 2 * d + 2 * tri(d);
@@ -17,6 +17,8 @@ int tune_len_of(int kind, int d) {
     case MMB_SAMPLER_BIA: return 1 + 2 * d;   // [iter, A[d], D[d]]  (BIATune, bia.jl:5-25)
     case MMB_SAMPLER_BHMC: return 2 * d + 3;  // [position[d], velocity[d], wallhits, wallcrosses, initialised]
                                               // (BHMCTune, bhmc.jl:5-19)
+    case MMB_SAMPLER_ABC: return 1 + nsim * (nstat + 2);  // [initialised, Tsim[nsim][T], epsilon[nsim],
+                                                          // epsilonprime[nsim]]  (ABCTune, abc.jl:5-18)
     default: return 0;
   }
 }
@@ -140,6 +142,11 @@ int mmb_get_tune(mmb_engine* e, double* tune) {
         t[0] = m[k];
         for (int i = 0; i < h.d; ++i) { t[1 + i] = ta[k * DP + i]; t[1 + h.d + i] = td[k * DP + i]; }
       }
+    } else if (h.spec.sampler == MMB_SAMPLER_ABC) {  // the device keeps the canonical row
+      std::vector<double> tr;
+      if ((rc = d2h(e, tr, h.hmc, K * h.tune_len))) return rc;
+      for (int64_t k = 0; k < K; ++k)
+        for (int i = 0; i < h.tune_len; ++i) tune[k * TL + off + i] = tr[k * h.tune_len + i];
     } else if (h.spec.sampler == MMB_SAMPLER_BHMC) {
       std::vector<double> tp, tv, tc;
       if ((rc = d2h(e, tp, h.sigma, K * DP)) || (rc = d2h(e, tv, h.accept, K * DP)) || (rc = d2h(e, tc, h.hmc, K * 2)))
@@ -186,6 +193,15 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
         if (!ok)
           return fail(e, MMB_E_ARG, "block %d chain %lld: a BHMC tune row is [position, velocity, wallhits, wallcrosses, "
                       "initialised] with whole counters >= 0 and initialised 0 or 1", (int)b + 1, (long long)k);
+      }
+      continue;
+    }
+    if (h.spec.sampler == MMB_SAMPLER_ABC) {
+      for (int64_t k = 0; k < K; ++k) {
+        const double t0 = tune[k * TL + off];
+        if (!(t0 == 0.0 || t0 == 1.0))
+          return fail(e, MMB_E_ARG, "block %d chain %lld: an ABC tune row is [initialised, Tsim, epsilon, epsilonprime] "
+                      "with initialised 0 or 1", (int)b + 1, (long long)k);
       }
       continue;
     }
@@ -279,6 +295,11 @@ int mmb_set_tune(mmb_engine* e, const double* tune) {
         for (int i = 0; i < h.d; ++i) { ta[k * DP + i] = t[1 + i]; td[k * DP + i] = t[1 + h.d + i]; }
       }
       if ((rc = h2d(e, h.sigma, ta)) || (rc = h2d(e, h.accept, td))) return rc;
+    } else if (h.spec.sampler == MMB_SAMPLER_ABC) {
+      std::vector<double> tr((size_t)K * h.tune_len);
+      for (int64_t k = 0; k < K; ++k)
+        for (int i = 0; i < h.tune_len; ++i) tr[k * h.tune_len + i] = tune[k * TL + off + i];
+      if ((rc = h2d(e, h.hmc, tr))) return rc;
     } else if (h.spec.sampler == MMB_SAMPLER_BHMC) {
       std::vector<double> tp(K * DP, 0.0), tv(K * DP, 0.0), tc(K * 2, 0.0);
       for (int64_t k = 0; k < K; ++k) {

@@ -164,6 +164,14 @@ struct Mdl<MMB_MODEL_IR> {
     }
   }
 
+  // the node and block tables, for the samplers that walk them themselves (samplers.h abc)
+  __device__ __forceinline__ static const mmb_ir_node& node_ref(const SweepArgs& A, int n) {
+    return ir_const_ref(A.ir_nodes, n);
+  }
+  __device__ __forceinline__ static const mmb_ir_block& block_ref(const SweepArgs& A, int b) {
+    return ir_const_ref(A.ir_blocks, b);
+  }
+
   // logpdf_sub of element i of a node at value x (distributionstruct.jl:138-140).  The constant term is
   // per element, except a sampled Binomial's (indexed by element and value) and Categorical's (its
   // probability table, indexed by value); a sampled discrete node's value is state, so its support is

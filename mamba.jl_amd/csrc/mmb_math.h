@@ -44,6 +44,20 @@
 #define MMB_SUB_PROPOSAL 5u /* RWM's non-Normal proposal variates (symdist.h): uniform #(8k + j) for coordinate k */
 #define MMB_SUB_SIMPLEX 6u  /* SliceSimplex's Dirichlet(1, ..., 1) draws: uniform #(32r + j) for element j of draw r */
 #define MMB_SUB_BINARY 7u   /* BMG / BMC3: the index set's uniforms #j; BIA: the proposal uniform #j of element j */
+/* ABC's simulated data (samplers.h abc, abc.h mmb_abc_block).  The tag is 32 bits, block * 16 + substream, so a
+ * block index has 28 bits; sampler blocks (< 8) and predict_math.h's node and element blocks (256 + n and
+ * 65536 (n + 1) + e, up to 2^28 - 1) leave no free range of block indices wide enough on the substreams 0..7,
+ * so ABC's variates live on two substreams of their own, where every block index is free:
+ *   block(b, k, i, j) = ((b (MMB_ABC_MAX_DRAW + 1) + k) MMB_ABC_MAX_NSIM + i) 32 + j   (< 2^22)
+ * b the sampler block, k the draw (0: the first update's simulation at the current values, 1..maxdraw: the
+ * candidates), i the simulation, j the data node's position among the block's data nodes (< 16) or 16 (randeps).
+ * Element e of data node j: the variate predict_math.h's mmb_pr_elem_on draws with sn = (block, MMB_SUB_ABC_N)
+ * and su = (block, MMB_SUB_ABC_U).  randeps: epsilonprime = -eps log1p(-u), u = uniform #0 of (block(b, k, i, 16),
+ * MMB_SUB_ABC_U).  The proposal of draw k = 1..maxdraw takes coordinate e's variate at index q = (k - 1) dim + e:
+ * normal #q of the block's MMB_SUB_NORMAL, or symdist.h's variate of coordinate q on MMB_SUB_PROPOSAL; its accept
+ * uniform is #(k - 1) of the block's MMB_SUB_UNIFORM.  Every variate is a function of its key alone. */
+#define MMB_SUB_ABC_N 8u
+#define MMB_SUB_ABC_U 9u
 
 #define MMB_LOG2PI 1.8378770664093454835606594728112352797
 #define MMB_TWOPI_HI 6.28318530717958623200e+00

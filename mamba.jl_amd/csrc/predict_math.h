@@ -95,39 +95,49 @@ MMB_HD double mmb_pr_gamma(double a, uint64_t seed, uint32_t chain, uint32_t ite
   return mmb_gamma_any(a, &sn, &su, &kn, &ku);
 }
 
+/* element e of a node of family fam and length len with parameters (a, b) in Distributions order, for the
+ * families that draw without a rejection loop: the normal of stream sn or the uniforms of stream su.  The
+ * body of mmb_pr_elem below, and of the ABC update's simulated data (samplers.h abc) on streams of its own. */
+MMB_HD double mmb_pr_elem_on(int fam, double a, double b, const mmb_rng* sn, const mmb_rng* su, int e, int len) {
+  const double NAN_ = __builtin_nan("");
+  switch (fam) {
+    case MMB_IR_NORMAL:
+    case MMB_IR_ISONORMAL:
+      if (!isfinite(a) || !isfinite(b) || b < 0.0) return NAN_;
+      return a + b * mmb_normal(sn, (uint32_t)e);
+    case MMB_IR_BERNOULLI:
+      if (!(a >= 0.0 && a <= 1.0)) return NAN_;
+      return mmb_uniform(su, (uint32_t)e) < a ? 1.0 : 0.0;
+    case MMB_IR_EXPONENTIAL:
+      if (!isfinite(a) || !(a > 0.0)) return NAN_;
+      return -a * mmb_log1p(-mmb_uniform(su, (uint32_t)e));
+    case MMB_IR_UNIFORM:
+      if (!isfinite(a) || !isfinite(b) || b < a) return NAN_;
+      return a + (b - a) * mmb_uniform(su, (uint32_t)e);
+    case MMB_IR_BINOMIAL:
+      return mmb_pr_binomial(a, b, su, (uint32_t)e, (uint32_t)len);
+    case MMB_IR_POISSON:
+      return mmb_pr_poisson(a, su, (uint32_t)e, (uint32_t)len);
+    default:
+      return NAN_;
+  }
+}
+
 /* element e of node n (family fam, length len) with parameters (a, b) in Distributions order */
 MMB_HD double mmb_pr_elem(int fam, double a, double b, uint64_t seed, uint32_t chain, uint32_t iter, int n, int e,
                           int len) {
   const double NAN_ = __builtin_nan("");
   switch (fam) {
     case MMB_IR_NORMAL:
-    case MMB_IR_ISONORMAL: {
-      if (!isfinite(a) || !isfinite(b) || b < 0.0) return NAN_;
-      const mmb_rng s = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_NORMAL);
-      return a + b * mmb_normal(&s, (uint32_t)e);
-    }
-    case MMB_IR_BERNOULLI: {
-      if (!(a >= 0.0 && a <= 1.0)) return NAN_;
-      const mmb_rng s = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_UNIFORM);
-      return mmb_uniform(&s, (uint32_t)e) < a ? 1.0 : 0.0;
-    }
-    case MMB_IR_EXPONENTIAL: {
-      if (!isfinite(a) || !(a > 0.0)) return NAN_;
-      const mmb_rng s = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_UNIFORM);
-      return -a * mmb_log1p(-mmb_uniform(&s, (uint32_t)e));
-    }
-    case MMB_IR_UNIFORM: {
-      if (!isfinite(a) || !isfinite(b) || b < a) return NAN_;
-      const mmb_rng s = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_UNIFORM);
-      return a + (b - a) * mmb_uniform(&s, (uint32_t)e);
-    }
-    case MMB_IR_BINOMIAL: {
-      const mmb_rng s = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_UNIFORM);
-      return mmb_pr_binomial(a, b, &s, (uint32_t)e, (uint32_t)len);
-    }
+    case MMB_IR_ISONORMAL:
+    case MMB_IR_BERNOULLI:
+    case MMB_IR_EXPONENTIAL:
+    case MMB_IR_UNIFORM:
+    case MMB_IR_BINOMIAL:
     case MMB_IR_POISSON: {
-      const mmb_rng s = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_UNIFORM);
-      return mmb_pr_poisson(a, &s, (uint32_t)e, (uint32_t)len);
+      const mmb_rng sn = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_NORMAL);
+      const mmb_rng su = mmb_rng_make(seed, chain, iter, mmb_pr_block(n), MMB_SUB_UNIFORM);
+      return mmb_pr_elem_on(fam, a, b, &sn, &su, e, len);
     }
     case MMB_IR_GAMMA:
     case MMB_IR_INVGAMMA:

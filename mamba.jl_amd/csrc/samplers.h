@@ -613,6 +613,245 @@ struct Smp {
     M::relist(B, s, g, v);
   }
 
+  // ---------------------------------------------------------------- ABC
+  // Approximate Bayesian computation (abc.jl:36-144) of the block's continuous nodes, d = B.d <= 32
+  // coordinates unlisted with transform, coordinate e on lane e (node-IR models).  No likelihood is
+  // evaluated: up to maxdraw = B.batchsize rounds of propose, simulate nsim = B.adapt data sets from the
+  // block's data nodes at the candidate, summarise them, measure the distance to the observed summaries,
+  // weight by the kernel density (abc.h), accept or reject.  proposal = B.form & 0xff, kernel =
+  // (B.form >> 8) & 0xff, randeps = bit 16, epsilon = B.scale, decay = B.beta, scale[d] per chain in
+  // B.t_sigma.  B.sep is the block's table (engine.cpp abc_table): [T, ns, nd, codes[ns], then per data
+  // node (node id, first statistic)].  Tune per chain: B.t_hmc, the canonical row [initialised,
+  // Tsim[nsim][T], epsilon[nsim], epsilonprime[nsim]].
+  //
+  // Summaries (abc_stats): element e of a data node sits on lane e % 32 in ascending e -- the observed
+  // value, or the variate mmb_pr_elem_on draws at the parameters the node's expressions give on the
+  // candidate state (s.prop), on the streams of (block, draw k, simulation i, data slot j), abc.h
+  // mmb_abc_block.  sum: lane partials in element order, then the 32-lane butterfly (g.sum); mean:
+  // sum / n; var: a second pass over the elements, the partials of (x - mean)^2 summed likewise, over
+  // n - 1; std: sqrt(var); minimum / maximum: lane partials from +-Inf, the butterfly with "the partner's
+  // value if it is smaller (larger) or NaN", then lane 0's result for every lane (the sign of a zero
+  // tie is lane 0's).  identity: the node's elements.  Statistic t of the concatenated summaries sits on
+  // lane t.  A lane's first element is kept in a register for the second pass; later ones (nodes of
+  // more than 32 elements) are formed again, which gives the same bits: every variate is a function of
+  // its key.  distance: sqrt of g.sum over the lanes' (Tsim_t - Tobs_t)^2, lanes >= T adding 0.
+  //
+  // The candidate's Tsim1[i] (statistic t on lane t), epsilon1[i] and epsilonprime1[i] (on lane i) stay
+  // in registers and reach the tune row only on accept.  The two chains of a wave leave the draw loop
+  // at their own k; every cross-lane step (DPP stages, 32-wide shuffles) stays within the chain's own 32
+  // lanes, and every branch around one is uniform over those 32 lanes.
+  __device__ __forceinline__ static double abc_jmax(double a, double b) {  // Julia max(a, b): NaN propagates
+    if (isnan(a)) return a;
+    if (isnan(b)) return b;
+    return b > a ? b : a;
+  }
+  template <int S_>
+  __device__ __forceinline__ static void abc_minmax_stage(double& lo, double& hi) {
+    const double ol = Grp<G>::template other_d<S_>(lo);
+    const double oh = Grp<G>::template other_d<S_>(hi);
+    lo = (ol < lo || ol != ol) ? ol : lo;
+    hi = (oh > hi || oh != oh) ? oh : hi;
+  }
+  template <bool SIM>
+  __device__ __forceinline__ static double abc_elem(const SweepArgs& A, const mmb_ir_node& N, int e, double sig,
+                                                    const double* vals, const St& s, const mmb_rng& sn,
+                                                    const mmb_rng& su, int lane) {
+    if constexpr (!SIM) {
+      (void)sig; (void)sn; (void)su; (void)lane;
+      return (N.fixed ? A.ir_pool + N.off : vals + N.off)[e];
+    } else {
+      const double pa = N.expr[0] >= 0 ? M::ev(A, N.expr[0], e, vals, s.stk, lane) : 0.0;
+      const double pb = N.family == MMB_IR_ISONORMAL
+                            ? sig
+                            : (N.expr[1] >= 0 ? M::ev(A, N.expr[1], e, vals, s.stk, lane) : 0.0);
+      return mmb_pr_elem_on(N.family, pa, pb, &sn, &su, e, N.len);
+    }
+  }
+  // the concatenated summaries, statistic t on lane t (0 on lanes >= T): observed (SIM = false), or
+  // simulated for draw k, simulation i, on the state `vals`: the chain state itself for the observed values
+  // and the first update's simulation (k = 0; the reference simulates from the model as it stands, not from
+  // the relisted invlink(link(value))), the candidate state for k >= 1
+  template <bool SIM>
+  __device__ __noinline__ static double abc_stats(const SweepArgs& A, const DBlock& B, const St& s, const double* vals,
+                                                  const Grp<G>& g, uint32_t chain, uint32_t it, int b, int k, int i) {
+    const int32_t* tab = B.sep;
+    const int ns = tab[1], nd = tab[2];
+    const int32_t* codes = tab + 3;
+    const int32_t* dn = tab + 3 + ns;
+    bool need_var = false, need_mm = false;
+    for (int q = 0; q < ns; ++q) {
+      need_var = need_var || codes[q] == MMB_ABC_VAR || codes[q] == MMB_ABC_STD;
+      need_mm = need_mm || codes[q] == MMB_ABC_MINIMUM || codes[q] == MMB_ABC_MAXIMUM;
+    }
+    double ts = 0.0;
+    for (int j = 0; j < nd; ++j) {
+      const mmb_ir_node& N = M::node_ref(A, dn[2 * j]);
+      const int t0 = dn[2 * j + 1], n = N.len;
+      const uint32_t blk = mmb_abc_block(b, k, i, j);
+      const mmb_rng sn = mmb_rng_make(A.seed, chain, it, blk, MMB_SUB_ABC_N);
+      const mmb_rng su = mmb_rng_make(A.seed, chain, it, blk, MMB_SUB_ABC_U);
+      double sig = 0.0;
+      if (SIM && N.family == MMB_IR_ISONORMAL) sig = M::ev(A, N.expr[1], 0, vals, s.stk, g.lane);
+      const double x0 = g.lane < n ? abc_elem<SIM>(A, N, g.lane, sig, vals, s, sn, su, g.lane) : 0.0;
+      if (codes[0] == MMB_ABC_IDENTITY) {  // n <= 32 here: T <= 32
+        const double xv = __shfl(x0, (g.lane - t0) & 31, 32);
+        ts = (g.lane >= t0 && g.lane < t0 + n) ? xv : ts;
+        continue;
+      }
+      double ps = 0.0, lo = __builtin_inf(), hi = -__builtin_inf();
+      for (int e = g.lane; e < n; e += G) {
+        const double xe = e == g.lane ? x0 : abc_elem<SIM>(A, N, e, sig, vals, s, sn, su, g.lane);
+        ps = ps + xe;
+        lo = (xe < lo || xe != xe) ? xe : lo;
+        hi = (xe > hi || xe != xe) ? xe : hi;
+      }
+      const double sum = g.sum(ps);
+      const double mean = sum / (double)n;
+      double var = 0.0;
+      if (need_var) {
+        double pq = 0.0;
+        for (int e = g.lane; e < n; e += G) {
+          const double xe = e == g.lane ? x0 : abc_elem<SIM>(A, N, e, sig, vals, s, sn, su, g.lane);
+          const double dv = xe - mean;
+          pq = pq + dv * dv;
+        }
+        var = g.sum(pq) / (double)(n - 1);
+      }
+      if (need_mm) {
+        abc_minmax_stage<0>(lo, hi); abc_minmax_stage<1>(lo, hi); abc_minmax_stage<2>(lo, hi);
+        abc_minmax_stage<3>(lo, hi); abc_minmax_stage<4>(lo, hi);
+        lo = __shfl(lo, 0, 32);
+        hi = __shfl(hi, 0, 32);
+      }
+      for (int q = 0; q < ns; ++q) {
+        const int cd = codes[q];
+        const double sv = cd == MMB_ABC_SUM ? sum : cd == MMB_ABC_MEAN ? mean : cd == MMB_ABC_VAR ? var
+                          : cd == MMB_ABC_STD ? sqrt(var) : cd == MMB_ABC_MINIMUM ? lo : hi;
+        ts = g.lane == t0 + q ? sv : ts;
+      }
+    }
+    return ts;
+  }
+  // logpdf(model, params, transform) (abc.jl:41, 103-104): the block's own nodes' terms in term order, with
+  // logpdf!'s early exit on a non-finite running sum; x is written into the candidate state first, where
+  // the data nodes' parameter expressions then read it
+  __device__ __noinline__ static double abc_prior(const SweepArgs& A, const DBlock& B, const St& s, const Grp<G>& g,
+                                                  const double* x) {
+    M::put(B, s, g.lane, x, s.prop, nullptr);
+    const mmb_ir_block& IB = M::block_ref(A, B.ir_blk);
+    double lp = 0.0;
+    for (int t = 0; t < IB.nterms; ++t) {
+      if (!IB.trans[t]) continue;
+      lp += M::template node_lp<false>(A, IB.term[t], s.prop, s.stk, g, B.transform);
+      if (!isfinite(lp)) break;
+    }
+    return lp;
+  }
+  __device__ __forceinline__ static double abc_dist(double ts, double tobs, int T, const Grp<G>& g) {
+    const double df = g.lane < T ? ts - tobs : 0.0;
+    return sqrt(g.sum(df * df));
+  }
+  __device__ static void abc(const SweepArgs& A, const DBlock& B, int c, uint32_t chain, int64_t it, int b,
+                             const mmb_rng& rn, const mmb_rng& ru, St& s, const Grp<G>& g) {
+    static_assert(G == 32 && R == 1, "ABC keeps one statistic per lane of a 32-lane group");
+    const int T = B.sep[0];
+    const int d = B.d, nsim = B.adapt, maxdraw = B.batchsize;
+    const int prop = B.form & 0xff, kern = (B.form >> 8) & 0xff;
+    const bool randeps = ((B.form >> 16) & 1) != 0;
+    const double eps = B.scale, decay = B.beta;
+    const uint32_t itk = (uint32_t)it;
+    double* row = B.t_hmc + (size_t)c * (size_t)(1 + nsim * (T + 2));
+    double* rowe = row + 1 + nsim * T;
+    const mmb_rng rp = mmb_rng_make(A.seed, chain, itk, (uint32_t)b, MMB_SUB_PROPOSAL);
+    double v[R], x[R];
+    M::unlist(B, s, g.lane, v);
+    const double lp0 = abc_prior(A, B, s, g, v);
+    const double tobs = abc_stats<false>(A, B, s, s.cur, g, chain, itk, b, 0, 0);
+    const bool first = row[0] == 0.0;
+    double pi0 = 0.0, e0 = 0.0;  // e0: the current epsilon[i] on lane i
+#pragma unroll 1
+    for (int i = 0; i < nsim; ++i) {
+      double ts, ei, epi, perr = 1.0, dd;
+      if (first) {  // abc.jl:63-83
+        ts = abc_stats<true>(A, B, s, s.cur, g, chain, itk, b, 0, i);
+        dd = abc_dist(ts, tobs, T, g);
+        ei = decay > 0.0 ? abc_jmax(eps, dd) : eps;
+        epi = ei;
+        if (randeps) {
+          const mmb_rng se = mmb_rng_make(A.seed, chain, itk, mmb_abc_block(b, 0, i, 16), MMB_SUB_ABC_U);
+          epi = -ei * mmb_log1p(-mmb_uniform(&se, 0u));
+          perr = mmb_abc_exp_pdf(ei, epi);
+        }
+        if (g.lane < T) row[1 + i * T + g.lane] = ts;
+        if (g.lane == i) {  // (the lanes that store them on accept: same lane, same address, program order)
+          rowe[i] = ei;
+          rowe[nsim + i] = epi;
+        }
+      } else {  // abc.jl:86-93
+        ts = g.lane < T ? row[1 + i * T + g.lane] : 0.0;
+        ei = rowe[i];
+        epi = rowe[nsim + i];
+        dd = abc_dist(ts, tobs, T, g);
+        if (randeps) perr = mmb_abc_exp_pdf(ei, epi);
+      }
+      pi0 = pi0 + mmb_abc_kernel_pdf(kern, epi, dd) * perr;
+      e0 = g.lane == i ? ei : e0;
+    }
+    double ts1[MMB_ABC_MAX_NSIM];
+#pragma unroll
+    for (int i = 0; i < MMB_ABC_MAX_NSIM; ++i) ts1[i] = 0.0;
+    double e1 = 0.0, ep1 = 0.0;  // the candidate's epsilon1[i], epsilonprime1[i] on lane i
+    bool acc = false;
+#pragma unroll 1
+    for (int k = 1; k <= maxdraw; ++k) {
+      double sc = 0.0, z = 0.0;
+      if (g.lane < d) {
+        const uint32_t q = (uint32_t)(k - 1) * (uint32_t)d + (uint32_t)g.lane;
+        sc = B.t_sigma[(size_t)c * DP + g.lane];
+        z = prop == MMB_RWM_NORMAL ? mmb_normal(&rn, q) : mmb_symdist(prop, &rp, q);
+      }
+      x[0] = v[0] + sc * z;
+      const double lp1 = abc_prior(A, B, s, g, x);
+      if (lp1 == -__builtin_inf()) continue;
+      double pi1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < MMB_ABC_MAX_NSIM; ++i) {
+        if (i < nsim) {
+          ts1[i] = abc_stats<true>(A, B, s, s.prop, g, chain, itk, b, k, i);
+          const double dd = abc_dist(ts1[i], tobs, T, g);
+          const double eo = __shfl(e0, i, 32);
+          const double ei = (1.0 - decay) * eo + decay * abc_jmax(eps, jmin(dd, eo));  // abc.jl:119-120
+          double epi = ei, perr = 1.0;
+          if (randeps) {
+            const mmb_rng se = mmb_rng_make(A.seed, chain, itk, mmb_abc_block(b, k, i, 16), MMB_SUB_ABC_U);
+            epi = -ei * mmb_log1p(-mmb_uniform(&se, 0u));
+            perr = mmb_abc_exp_pdf(ei, epi);
+          }
+          pi1 = pi1 + mmb_abc_kernel_pdf(kern, epi, dd) * perr;
+          e1 = g.lane == i ? ei : e1;
+          ep1 = g.lane == i ? epi : ep1;
+        }
+      }
+      if (mmb_uniform(&ru, (uint32_t)(k - 1)) < pi1 / pi0 * mmb_exp(lp1 - lp0)) {
+        acc = true;
+        break;
+      }
+    }
+    if (acc) {
+      v[0] = x[0];
+#pragma unroll
+      for (int i = 0; i < MMB_ABC_MAX_NSIM; ++i)
+        if (i < nsim && g.lane < T) row[1 + i * T + g.lane] = ts1[i];
+      if (g.lane < nsim) {
+        rowe[g.lane] = e1;
+        rowe[nsim + g.lane] = ep1;
+      }
+    }
+    if (first && g.lane == 0) row[0] = 1.0;
+    bin_count(B, c, acc, g);
+    M::relist(B, s, g, v);
+  }
+
   // ---------------------------------------------------------------- SliceSimplex
   // slicesimplex.jl:86-122 (sample!, makefirstsimplex, shrinksimplex) for the block's one Dirichlet node
   // of k = B.d <= 32 elements (node-IR models; M::ssx_* in ir.h), the reference's linear solves

@@ -178,6 +178,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& A) {
             S::bhmc(A, B, c, rn, ri, s, l, g);
           }
           break;
+        case MMB_SAMPLER_ABC:
+          if constexpr ((KINDS >> MMB_SAMPLER_ABC) & 1u) S::abc(A, B, c, chain, it, b, rn, ru, s, g);
+          break;
         case MMB_SAMPLER_GIBBS: if constexpr ((KINDS >> MMB_SAMPLER_GIBBS) & 1u) {
           const mmb_rng gn = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_N);
           const mmb_rng gu = mmb_rng_make(A.seed, chain, (uint32_t)it, (uint32_t)b, MMB_SUB_GAMMA_U);
@@ -251,4 +254,6 @@ constexpr unsigned K_SIMPLEX = 1u << MMB_SAMPLER_SLICESIMPLEX;
 constexpr unsigned K_BIN = (1u << MMB_SAMPLER_BMG) | (1u << MMB_SAMPLER_BMC3) | (1u << MMB_SAMPLER_BIA);
 // BHMC likewise: one further instantiation, which holds every other kind
 constexpr unsigned K_BHMC = 1u << MMB_SAMPLER_BHMC;
+// ABC likewise: one further instantiation, which holds every other kind
+constexpr unsigned K_ABC = 1u << MMB_SAMPLER_ABC;
 

@@ -163,6 +163,8 @@ hipError_t mmb_launch_sweep(int model, unsigned kinds, const SweepArgs& A, hipSt
     return launch<MMB_MODEL_RATS, K_ALL>(A, st, TB);
   }
   if (model == MMB_MODEL_IR) {
+    if (kinds & K_ABC)
+      return launch<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX | K_BIN | K_BHMC | K_ABC>(A, st, 128);
     if (kinds & K_BHMC) return launch<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX | K_BIN | K_BHMC>(A, st, 128);
     if (kinds & K_BIN) return launch<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX | K_BIN>(A, st, 128);
     if (kinds & K_SIMPLEX) return launch<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX>(A, st, 128);
@@ -195,6 +197,8 @@ hipError_t mmb_sweep_shape(int model, unsigned kinds, const SweepArgs& A, int* n
     return shape<MMB_MODEL_RATS, K_ALL>(A, TB, nwg, wg_per_cu);
   }
   if (model == MMB_MODEL_IR) {
+    if (kinds & K_ABC)
+      return shape<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX | K_BIN | K_BHMC | K_ABC>(A, 128, nwg, wg_per_cu);
     if (kinds & K_BHMC)
       return shape<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX | K_BIN | K_BHMC>(A, 128, nwg, wg_per_cu);
     if (kinds & K_BIN) return shape<MMB_MODEL_IR, K_IR | K_RWM | K_DGS | K_SIMPLEX | K_BIN>(A, 128, nwg, wg_per_cu);

@@ -446,6 +446,8 @@ class Model(_BaseModel):
                     raise ArgumentError(f"Dirichlet node {n} cannot be sampled by {s!r}: use SliceSimplex")
                 elif fam in _DISCRETE:
                     raise ArgumentError(f"discrete node {n} cannot be sampled by {s!r}: use DGS")
+                elif s.kind == abi.MMB_SAMPLER_ABC and fam not in _SAMPLEABLE:
+                    raise ArgumentError(f"ABC: node {n} is not a continuous sampleable node")
                 elif fam not in _SAMPLEABLE:
                     raise ArgumentError(f"node {n}: its distribution family cannot be sampled by these samplers")
         self.discrete = [n for n in self.params if n in by_dgs]
@@ -809,6 +811,7 @@ class _Lowering:
         ids = {n: i for i, n in enumerate(m.order)}
         nodes = (abi.IrNode * len(m.order))()
         parents = {}
+        simulated_only = set()
         for n in m.order:
             N = nodes[ids[n]]
             N.expr[0] = N.expr[1] = N.expr[2] = -1
@@ -847,8 +850,15 @@ class _Lowering:
             if dist.fam == abi.MMB_IR_UNIFORM:
                 lo, hi = self.host_value(ps[0], 1), self.host_value(ps[1], 1)
                 if lo is None or hi is None:
-                    raise ArgumentError(f"Uniform bounds of {n} must be constants or data")
-                N.lo, N.hi = float(lo[0]), float(hi[0])
+                    if n in m.params:
+                        raise ArgumentError(f"Uniform bounds of {n} must be constants or data")
+                    # an observed Uniform node whose bounds read sampled nodes has no constant support to
+                    # evaluate its density on: only ABC blocks, which simulate it from the bound expressions
+                    # and never evaluate its density, may hold it as a target (checked below)
+                    simulated_only.add(n)
+                    N.lo = N.hi = float("nan")
+                else:
+                    N.lo, N.hi = float(lo[0]), float(hi[0])
             if dist.fam in _DISCRETE and n in m.params:
                 # sampled by a DGS block: the support lo..hi, at most one value per lane of the group
                 if dist.fam == abi.MMB_IR_POISSON:
@@ -927,6 +937,10 @@ class _Lowering:
         ir = abi.IrModel()
         for b, s in enumerate(m.samplers):
             targets = {c for p in s.params for c in children[p]}
+            for t in sorted(targets & simulated_only):
+                if s.kind != abi.MMB_SAMPLER_ABC:
+                    raise ArgumentError(f"Uniform bounds of {t} must be constants or data: {s!r} evaluates its "
+                                        "density (only ABC blocks, which simulate it, take such a node)")
             terms = [p for p in s.params if p not in targets] + [t for t in topo if t in targets]
             if len(terms) > abi.MMB_IR_MAX_TERMS:
                 raise ArgumentError("too many nodes in one block's logpdf!")
@@ -935,6 +949,8 @@ class _Lowering:
                 ir.blocks[b].term[t] = ids[nm]
                 ir.blocks[b].trans[t] = int(nm in s.params)
             s.targets = [t for t in topo if t in targets]
+            if s.kind == abi.MMB_SAMPLER_ABC:  # abc.jl:49-51: the data nodes, in the block's term order
+                s.resolve_abc([(t, m.traced[t].fam, m.lens[t]) for t in terms if t not in s.params])
             if s.kind == abi.MMB_SAMPLER_GIBBS:
                 self.gibbs(ir.blocks[b], s)
         mon, names = [], []
@@ -1213,3 +1229,30 @@ def eyes_scheme():
     from .samplers import DGS, Slice, SliceSimplex
     return [DGS("T"), Slice(["lambda0", "theta"], [5.0, 1.0]), Slice("s2", 2.0, transform=True),
             SliceSimplex("P", scale=0.75)]
+
+
+def line_abc_model():
+    """doc/examples/line_abc.jl:13-20 written in the IR (xmat * beta as beta[1] + beta[2] x, inlined into y)."""
+    return Model(
+        y=Stochastic(1, lambda x, beta, s2: MvNormal(beta[1] + beta[2] * x, sqrt(s2)), False),
+        beta=Stochastic(1, lambda: MvNormal(2, math.sqrt(100))),
+        s2=Stochastic(lambda: InverseGamma(0.01, 0.01)))
+
+
+def line_abc_inputs():
+    """doc/examples/line_abc.jl:4-7 (y is the observed node's initial value: line_abc_inits)."""
+    return {"x": [1.0, 2.0, 3.0, 4.0, 5.0]}
+
+
+def line_abc_inits(chains, seed=1):
+    """doc/examples/line_abc.jl:24-31: beta ~ Normal(0, 1), s2 ~ Gamma(1, 1) per chain."""
+    rng = np.random.default_rng(seed)
+    return [{"y": [1.0, 3.0, 3.0, 3.0, 5.0], "beta": rng.normal(0.0, 1.0, 2), "s2": float(rng.gamma(1.0, 1.0))}
+            for _ in range(chains)]
+
+
+def line_abc_scheme(maxdraw=100, nsim=3):
+    """doc/examples/line_abc.jl:35-48: summary1 = identity, summary2 = x -> [mean(x); sqrt(var(x))]."""
+    from .samplers import ABC, Epanechnikov
+    return [ABC("beta", [0.5, 0.25], "identity", 0.5, kernel="Normal", maxdraw=maxdraw, nsim=nsim),
+            ABC("s2", 0.5, ("mean", "std"), 0.1, kernel=Epanechnikov, maxdraw=maxdraw, nsim=nsim)]

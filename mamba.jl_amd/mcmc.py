@@ -173,12 +173,13 @@ class Engine:
 
     def accept_stats(self):
         """Update and accept counters since init_chains of every block that has a Metropolis accept step
-        and counts it (mmb_rwm_stats): RWM, BMG, BMC3, BIA and BHMC blocks, one dict per block keyed by block
+        and counts it (mmb_rwm_stats): RWM, BMG, BMC3, BIA, BHMC and ABC blocks, one dict per block keyed by block
         index, summed over the chains.  A BMG block of one element has no accept step (bmg.jl:83-84):
         every update counts as accepted.  A BHMC block's accepts are the updates that ran to traveltime:
-        updates - accepts of them stalled and left the chain as it was."""
+        updates - accepts of them stalled and left the chain as it was.  An ABC block's accepts are the updates
+        that took one of their candidates."""
         kinds = (abi.MMB_SAMPLER_RWM, abi.MMB_SAMPLER_BMG, abi.MMB_SAMPLER_BMC3, abi.MMB_SAMPLER_BIA,
-                 abi.MMB_SAMPLER_BHMC)
+                 abi.MMB_SAMPLER_BHMC, abi.MMB_SAMPLER_ABC)
         v = (C.c_int64 * (abi.MMB_MAX_BLOCKS * 2))()
         self._chk(self.lib.mmb_rwm_stats(self.h, v))
         return {b: {"updates": v[2 * b], "accepts": v[2 * b + 1],

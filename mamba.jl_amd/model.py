@@ -52,6 +52,8 @@ class Model:
                 raise ArgumentError(f"{s!r} samples the binary nodes of node-IR models (ir.Model) only")
             if s.kind == abi.MMB_SAMPLER_SLICESIMPLEX:
                 raise ArgumentError("SliceSimplex samples the Dirichlet nodes of node-IR models (ir.Model) only")
+            if s.kind == abi.MMB_SAMPLER_ABC:
+                raise ArgumentError("ABC simulates the data nodes of node-IR models (ir.Model) only")
             if len(s.params) > abi.MMB_MAX_NODES_PER_BLOCK:
                 raise ArgumentError("too many nodes in one block")
             for p in s.params:

@@ -21,6 +21,9 @@ Argument meaning, defaults and validation errors follow the reference:
                   always adapt (node-IR models)               src/samplers/bia.jl:18-24, bia.jl:55-63
   BHMC(params, traveltime, refresh=False)  -- binary Hamiltonian Monte Carlo on one Bernoulli node
                   (node-IR models; the particle is the tune state)      src/samplers/bhmc.jl:35-43
+  ABC(params, scale, summary, epsilon, kernel=SymUniform, dist=None, proposal=Normal, maxdraw=1, nsim=1,
+      decay=1.0, randeps=False)  -- approximate Bayesian computation: no likelihood, the block's data
+                  nodes are simulated and summarised (node-IR models)   src/samplers/abc.jl:23-29
   Gibbs(params)  -- a user `Sampler(params, f)` whose f is the node's conjugate full
                     conditional (doc/tutorial/line.jl:27-45); lowered per model.
 """
@@ -121,17 +124,49 @@ class Sampler:
             if not (math.isfinite(self.scale) and 0.0 < self.scale <= abi.MMB_BHMC_MAX_TRAVELTIME):
                 raise ArgumentError("traveltime is not finite, > 0 and <= 128 pi")
 
+        if self.kind == abi.MMB_SAMPLER_ABC and not (self.abc_scale.size == 1 or self.abc_scale.size == dim):
+            raise ArgumentError(f"length(scale) differs from variate length {dim}")
+
+    def resolve_abc(self, data):
+        """The block's data nodes, known once the model is lowered (ir.py): `data` lists (name, family, length)
+        in the block's term order.  Checks them (abc.jl:49-58 and the documented caps) and fixes T."""
+        if not data:
+            raise ArgumentError(f"ABC({self.params}) needs at least one data node: a stochastic node among the "
+                                "block's targets that is not one of its params")
+        if len(data) > abi.MMB_ABC_MAX_DATA:
+            raise ArgumentError(f"ABC({self.params}): at most {abi.MMB_ABC_MAX_DATA} data nodes")
+        ident = self.abc_codes[0] == abi.MMB_ABC_IDENTITY
+        needs2 = any(c in (abi.MMB_ABC_VAR, abi.MMB_ABC_STD) for c in self.abc_codes)
+        T = 0
+        for name, fam, ln in data:
+            if fam not in ABC_DATA_FAMILIES:
+                raise ArgumentError(f"ABC cannot simulate data node {name}: {ABC_REFUSED_FAMILIES.get(fam, 'such')} "
+                                    "data nodes are not supported")
+            if needs2 and ln < 2:
+                raise ArgumentError(f"the var and std summaries need data nodes of >= 2 elements ({name} has {ln})")
+            T += ln if ident else len(self.abc_codes)
+        if not 1 <= T <= abi.MMB_ABC_MAX_T:
+            raise ArgumentError(f"the total summary length {T} is not in 1..{abi.MMB_ABC_MAX_T}")
+        self.abc_data, self.abc_T = [d[0] for d in data], T
+
     def spec_tuning(self, dim):
         """`tuning` as the block spec carries it: RWM's scalar scale is broadcast to the variate length
         (the engine takes scale[dim]); every other kind passes its vector as it is."""
         if self.kind == abi.MMB_SAMPLER_RWM and self.tuning.size == 1:
             return np.full(dim, self.tuning[0])
+        if self.kind == abi.MMB_SAMPLER_ABC:  # scale[dim], then the summary codes
+            sc = np.full(dim, self.abc_scale[0]) if self.abc_scale.size == 1 else self.abc_scale
+            return np.concatenate([sc, np.asarray(self.abc_codes, dtype=np.float64)])
         return self.tuning
 
     def tune_len(self, dim):
         """Length of the block's canonical tune row (csrc/engine_tune.cpp tune_len_of) for a variate of
         `dim` elements."""
         tri = dim * (dim + 1) // 2
+        if self.kind == abi.MMB_SAMPLER_ABC:  # [initialised, Tsim[nsim][T], epsilon[nsim], epsilonprime[nsim]]
+            if getattr(self, "abc_T", None) is None:
+                raise ArgumentError("an ABC block's tune row is known once its model has its initial values")
+            return 1 + self.nsteps * (self.abc_T + 2)
         return {abi.MMB_SAMPLER_AMWG: 2 + 2 * dim, abi.MMB_SAMPLER_AMM: 4 + 2 * dim + 2 * tri, abi.MMB_SAMPLER_NUTS: 9,
                 abi.MMB_SAMPLER_HMC: 2, abi.MMB_SAMPLER_MALA: 1, abi.MMB_SAMPLER_RWM: dim,
                 abi.MMB_SAMPLER_BIA: 1 + 2 * dim, abi.MMB_SAMPLER_BHMC: 2 * dim + 3}.get(self.kind, 0)
@@ -142,7 +177,7 @@ class Sampler:
     @property
     def name(self):
         return {1: "AMWG", 2: "AMM", 3: "NUTS", 4: "Slice", 5: "Gibbs", 6: "HMC", 7: "MALA", 8: "RWM", 9: "DGS",
-                10: "SliceSimplex", 11: "BMG", 12: "BMC3", 13: "BIA", 14: "BHMC"}[self.kind]
+                10: "SliceSimplex", 11: "BMG", 12: "BMC3", 13: "BIA", 14: "BHMC", 15: "ABC"}[self.kind]
 
 
 def AMWG(params, sigma, adapt="all", batchsize=50, target=0.44):
@@ -333,6 +368,79 @@ def BHMC(params, traveltime, refresh=False):
     except (TypeError, ValueError):
         raise ArgumentError("traveltime is a number") from None
     s.traveltime, s.refresh = s.scale, refresh
+    return s
+
+
+ABC_SUMMARIES = {"identity": abi.MMB_ABC_IDENTITY, "sum": abi.MMB_ABC_SUM, "mean": abi.MMB_ABC_MEAN,
+                 "var": abi.MMB_ABC_VAR, "std": abi.MMB_ABC_STD, "minimum": abi.MMB_ABC_MINIMUM,
+                 "maximum": abi.MMB_ABC_MAXIMUM}
+ABC_DATA_FAMILIES = (abi.MMB_IR_NORMAL, abi.MMB_IR_ISONORMAL, abi.MMB_IR_BERNOULLI, abi.MMB_IR_BINOMIAL,
+                     abi.MMB_IR_POISSON, abi.MMB_IR_EXPONENTIAL, abi.MMB_IR_UNIFORM)
+ABC_REFUSED_FAMILIES = {abi.MMB_IR_GAMMA: "Gamma", abi.MMB_IR_INVGAMMA: "InverseGamma", abi.MMB_IR_BETA: "Beta",
+                        abi.MMB_IR_CATEGORICAL: "Categorical", abi.MMB_IR_DISCRETEUNIFORM: "DiscreteUniform",
+                        abi.MMB_IR_DIRICHLET: "Dirichlet"}
+
+
+def ABC(params, scale, summary, epsilon, kernel=SymUniform, dist=None, proposal=Normal, maxdraw=1, nsim=1, decay=1.0,
+        randeps=False):
+    """ABC(params, scale, summary, epsilon; kernel, dist, proposal, maxdraw, nsim, decay, randeps) -- abc.jl:23-147:
+    approximate Bayesian computation on the continuous nodes of `params` (unlisted with transform).  Up to
+    `maxdraw` candidates theta0 + scale .* rand(proposal(0, 1)) per update; for each, `nsim` data sets are
+    simulated from the block's data nodes (the stochastic nodes among its targets that are not params),
+    summarised, and weighed by kernel(0, tolerance) at the distance sqrt(sumabs2(Tsim - Tobs)) to the observed
+    summaries; the tolerance decreases towards `epsilon` at rate `decay`, and with `randeps` is drawn from
+    Exponential(tolerance).  `summary`: a name or a tuple of names out of identity (alone), sum, mean, var, std,
+    minimum, maximum -- each data node's summary is the listed statistics, and the nodes' summaries are
+    concatenated (at most 32 values).  `dist`: None, the reference's default.  `kernel`, `proposal`: Normal or a
+    SymDistributionType name.  Tune row [initialised, Tsim[nsim][T], epsilon[nsim], epsilonprime[nsim]].
+    Node-IR models only."""
+    names = {k.lower(): v for k, v in RWM_PROPOSALS.items()}
+    try:
+        decay = float(decay)
+    except (TypeError, ValueError):
+        raise ArgumentError("decay is not in [0, 1]") from None
+    if not 0.0 <= decay <= 1.0:
+        raise ArgumentError("decay is not in [0, 1]")
+    if dist is not None:
+        raise ArgumentError("dist: only None, the reference's default sqrt(sumabs2(Tsim - Tobs)), is supported")
+    kern = names.get(str(kernel).lstrip(":").lower())
+    if kern is None:
+        raise ArgumentError(f"unsupported kernel {kernel}: one of {', '.join(RWM_PROPOSALS)}")
+    prop = names.get(str(proposal).lstrip(":").lower())
+    if prop is None:
+        raise ArgumentError(f"unsupported proposal {proposal}: one of {', '.join(RWM_PROPOSALS)}")
+    if not isinstance(randeps, (bool, np.bool_)):
+        raise ArgumentError("randeps is True or False")
+    try:
+        eps = float(epsilon)
+    except (TypeError, ValueError):
+        raise ArgumentError("epsilon is not finite and > 0") from None
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ArgumentError("epsilon is not finite and > 0")
+    for nm, val, cap in (("maxdraw", maxdraw, abi.MMB_ABC_MAX_DRAW), ("nsim", nsim, abi.MMB_ABC_MAX_NSIM)):
+        if isinstance(val, (bool, np.bool_)) or not isinstance(val, (int, np.integer)) or not 1 <= val <= cap:
+            raise ArgumentError(f"{nm} is not an integer in 1..{cap}")
+    codes = []
+    for nm in ([summary] if isinstance(summary, str) else list(summary)):
+        cd = ABC_SUMMARIES.get(str(nm).lstrip(":").lower()) if isinstance(nm, str) else None
+        if cd is None:
+            raise ArgumentError(f"unsupported summary {nm}: one of {', '.join(ABC_SUMMARIES)}")
+        codes.append(cd)
+    if not 1 <= len(codes) <= abi.MMB_ABC_MAX_SUMMARY:
+        raise ArgumentError(f"summary lists 1..{abi.MMB_ABC_MAX_SUMMARY} statistics")
+    if abi.MMB_ABC_IDENTITY in codes and len(codes) != 1:
+        raise ArgumentError("the identity summary may only stand alone")
+    try:
+        sc = np.atleast_1d(np.asarray(scale, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ArgumentError("scale must be a finite non-negative scalar or vector") from None
+    if sc.ndim != 1 or sc.size < 1 or not (np.isfinite(sc).all() and (sc >= 0.0).all()):
+        raise ArgumentError("scale must be a finite non-negative scalar or vector")
+    s = Sampler(params, abi.MMB_SAMPLER_ABC, abi.MMB_ADAPT_NONE, sc, form=prop | kern << 8 | int(bool(randeps)) << 16,
+                transform=True, batchsize=int(maxdraw), nsteps=int(nsim), beta=decay, epsilon=eps)
+    s.abc_scale, s.abc_codes, s.abc_T, s.abc_data = sc, codes, None, None
+    s.maxdraw, s.nsim, s.decay, s.randeps = int(maxdraw), int(nsim), decay, bool(randeps)
+    s.kernel, s.proposal = kern, prop
     return s
 
 
